@@ -181,6 +181,9 @@ def main():
     ap.add_argument("--regularization", default="", choices=["", "FROBENIUS", "PLANE", "MIN_EIG", "NORMALIZED_MIN_EIG", "NONE"],
                     help="fast_gicp RegularizationMethod of the GICP covariances (default: FROBENIUS, the constructor default hdl_graph_slam runs with; the "
                          "others take k_knn_cov's second instantiation with a 3x3 eigen-decomposition per point)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, rank 0 writes what the primary record's last timed step returned "
+                    "to its caller (a sharded batch: the records of ALL candidates) as DIR/<name>.npy (float32 / float64), for output-for-output "
+                    "comparison of two builds on the same seeded inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=3, help="units registered by the CPU oracle for cpu_baseline")
     args = ap.parse_args()
@@ -242,7 +245,10 @@ def main():
         out = run_single_align(ctx)
     else:
         out = run_odometry(ctx)
+    last_step = out.pop("_last_step")
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_step)
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
@@ -299,6 +305,36 @@ def base_line(ctx, value, unit, steps, dt, dtype, workload, extra_config):
             "scaling": "weak", "vs_baseline": None, "dtype": dtype,
             "data": "synthetic" if not ctx["emulated"] else "synthetic (EMULATED ON THE CPU - not a measurement)",
             "config": dict({"workload": workload, "baseline_config": a.config if a.config else "metric (config 3's scan size in config 4's batch shape)"}, **extra_config)}
+
+
+RECORD_FIELDS = ("final_transformation", "converged", "iterations", "error", "fitness_score", "num_inliers", "candidate_id", "lm_tries")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def record_outputs(rec, best=None):
+    """What a caller of the timed path receives: the hgs_result records (one per registration; final_transformation column-major, as the
+    C-ABI returns it) field by field, and for a batch the candidate the sequential rule selects.  Stored in the line's private `_last_step`."""
+    rec = np.atleast_1d(rec)
+    out = {f: rec[f] for f in RECORD_FIELDS}
+    if best is not None:
+        out["best_candidate"] = np.array([best])
+    return out
+
+
+def single_record(L, r):
+    """An hgs_result returned by align() as a one-element array of the batch record type."""
+    return np.frombuffer(bytes(r), dtype=L.RESULT_DTYPE, count=1)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: DIR/<name>.npy per array; float32 stays float32, every other type is written as float64 (exact for the integer fields)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 # ============================================================================================== loop-closure batch (default, config 4)
@@ -402,7 +438,7 @@ def measure_single_process(ctx, method, B, steps):
     out["n_gpus"] = n_eng
     out["scaling"] = "strong" if cfg4 else "weak"
     out.update({"step_ms": percentiles(per), "timed_region_s": round(dt, 3), "converged": int(np.sum(rec["converged"])), "mean_iterations": float(np.mean(rec["iterations"])),
-                "best_candidate": int(best), "roofline": None, "cpu_baseline": None})
+                "best_candidate": int(best), "roofline": None, "cpu_baseline": None, "_last_step": record_outputs(rec, best)})
     for c in d_cands:
         c.close()
     m.close()
@@ -458,6 +494,8 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
                 g[2, 3] = 0.0
         return wl, reg.upload(wl.target), [reg.upload(c) for c in wl.candidates]
 
+    gathered = {}   # the records of ALL candidates of the latest step (what a caller of the sharded path receives): --dump-outputs
+
     def make_step(wl, d_target, d_cands):
         def step(cold=True):
             d_target.invalidate()           # the query keyframe is new in every detection
@@ -468,12 +506,14 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
             ids = np.arange(rank, world * B, world, dtype=np.int32)   # candidate c lives on rank c mod world
             if shard is not None and exchange["kind"] == HGS_EXCHANGE:
                 allrec, best = reg.loop_match_batch_sharded(d_cands, ids, wl.guesses, world * B, fit_range)
+                gathered["records"] = allrec
                 return allrec[ids], best
             rec, best = reg.loop_match_batch(d_cands, wl.guesses, fit_range)
             if shard is not None:
                 rec["candidate_id"] = ids
                 allrec = shard.gather_records(rec, world * B)
                 best = ctx["select_best"](allrec)
+            gathered["records"] = rec if shard is None else allrec
             return rec, best
         return step
 
@@ -534,6 +574,7 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
         step()
         dt, per_step, rec, best = timed(step, steps)
     dt_rank = dt
+    last_records = gathered["records"]   # of the last timed step: the steps below (resident, profiled, other seeds) run step() again
     dt = max_over_ranks(ctx, dt)
 
     # ---- informational: the same batch with the candidate keyframes' index + covariances kept resident between detections
@@ -698,7 +739,7 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
                 "converged": int(np.sum(rec["converged"])), "mean_iterations": float(np.mean(rec["iterations"])),
                 "mean_linearizations": float(np.mean(rec["lm_tries"])), "best_candidate": int(best),
                 "num_inliers_mean": float(np.mean(rec["num_inliers"])),
-                "roofline": roofline, "cpu_baseline": cpu})
+                "roofline": roofline, "cpu_baseline": cpu, "_last_step": record_outputs(last_records, best)})
     for c in d_cands:
         c.close()
     d_target.close()
@@ -819,7 +860,7 @@ def run_single_align(ctx):
                 "value_mean_std_over_seeds": [round(float(np.mean(by_seed)), 2), round(float(np.std(by_seed)), 2)],
                 "iterations": int(r.iterations), "lm_tries": int(r.lm_tries), "converged": int(r.converged),
                 "pose_error_vs_ground_truth": {"translation_m": round(err_t, 5), "rotation_rad": round(err_r, 6)},
-                "roofline": roofline, "cpu_baseline": cpu})
+                "roofline": roofline, "cpu_baseline": cpu, "_last_step": record_outputs(single_record(L, r))})
     reg.close()
     return out
 
@@ -953,6 +994,7 @@ def odometry_at_speed(ctx, speed, n_seeds, with_cpu, pipeline="raw"):
         return dt, per, its, err, stream, od, est
 
     dt, per_step, its, err, stream, od, est = run(0, a.warmup, steps)
+    last_step = dict(record_outputs(single_record(L, od.last_result)), odom=est[-1])   # the last sweep: its registration record and the pose matching() returned
     dt = max_over_ranks(ctx, dt)
     n_pts = int(np.mean([len(c) for c in stream.scans]))
 
@@ -1026,7 +1068,7 @@ def odometry_at_speed(ctx, speed, n_seeds, with_cpu, pipeline="raw"):
                                                      "distance_travelled_m": round(speed / 10.0 * max(len(err) - 1, 1), 2),
                                                      # final error below 2 % of the distance travelled (and 0.25 m): the criterion of profiles/r06_ndt_tracking.md
                                                      "keeps_track": bool(err[-1][0] < max(0.25, 0.02 * speed / 10.0 * max(len(err) - 1, 1)))},
-                "oracle_stream": oracle_stream, "roofline": roofline, "cpu_baseline": cpu})
+                "oracle_stream": oracle_stream, "roofline": roofline, "cpu_baseline": cpu, "_last_step": last_step})
     reg.close()
     return out
 

@@ -2,9 +2,9 @@
 the patched src/hdl_graph_slam/registrations.cpp + a driver that includes the patched include/hdl_graph_slam/loop_detector.hpp
 (tests/cpp/integration_main.cpp) against the stand-in headers of tests/mock_ros, tests/mock_pcl, tests/mock_eigen.
 
-The reference tree exists only in the build container (/root/reference): the binaries land in integration/_build/ (git-ignored, like every
-built artefact; NOT gpurun-ignored, so they travel to the GPU box the way the .so files do) and the `-m gpu` test runs the prebuilt one.
-The patched scratch copy lives in a temporary directory and is deleted: no reference source enters this repository."""
+The reference tree exists only where the project is built, not on the GPU machine: __graft_entry__.build() puts the binaries under
+oracle/_ref/integration/ (git-ignored; the built tree, oracle/_ref/ included, is what the GPU machine receives) and the `-m gpu` test runs
+the prebuilt one.  The patched scratch copy lives in a temporary directory and is deleted: no reference source enters this repository."""
 from __future__ import annotations
 
 import os
@@ -15,7 +15,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = "/root/reference"
 PATCH = os.path.join(ROOT, "integration", "hdl_graph_slam_hip.patch")
-OUT = os.path.join(ROOT, "integration", "_build")
+OUT = os.path.join(ROOT, "oracle", "_ref", "integration")
 PATCHED = ["CMakeLists.txt", "src/hdl_graph_slam/registrations.cpp", "include/hdl_graph_slam/loop_detector.hpp", "apps/scan_matching_odometry_nodelet.cpp",
            "src/hdl_graph_slam/information_matrix_calculator.cpp", "src/hdl_graph_slam/map_cloud_generator.cpp", "apps/prefiltering_nodelet.cpp"]
 UNTOUCHED = ["include/hdl_graph_slam/registrations.hpp", "include/hdl_graph_slam/keyframe.hpp", "include/hdl_graph_slam/graph_slam.hpp", "include/hdl_graph_slam/ros_utils.hpp",

@@ -1,14 +1,15 @@
-"""TEST INFRASTRUCTURE: builds tests/_refpin/refpin_main = tests/cpp/refpin_main.cpp + two UNMODIFIED reference translation units,
+"""TEST INFRASTRUCTURE: builds oracle/_ref/refpin/refpin_main = tests/cpp/refpin_main.cpp + two UNMODIFIED reference translation units,
 compiled from where they lie under /root/reference (no reference source enters this repository):
 
     src/hdl_graph_slam/information_matrix_calculator.cpp      calc_fitness_score (:49-80), calc_information_matrix (:25-47)
     src/hdl_graph_slam/keyframe.cpp                           KeyFrame::save (:21-58), KeyFrame::load (:60-145)
 
-against the stand-in ROS / PCL / Eigen / g2o / boost headers of tests/mock_* (none of the real ones exist in this image).  This is NOT an
-`oracle/_ref` build of the reference's engines (ndt_omp / fast_gicp / PCL are absent and unbuildable): it runs the only two
+against the stand-in ROS / PCL / Eigen / g2o / boost headers of tests/mock_* (none of the real ones exist in this image).  It is not a
+build of the reference's engines (ndt_omp / fast_gicp / PCL are absent and unbuildable): it runs the only two
 pieces of the hot path's arithmetic / data format that live in the reference tree itself, so that `oracle/`, `keyframe_io.py` and the HIP path
-can be checked against reference code executed here instead of against our restatement alone.  The binary is git-ignored (tests/_refpin/)
-and travels to the GPU box like the other built artefacts; the vectors it produced are committed under tests/golden/ (make_refpin_golden.py).
+can be checked against reference code executed here instead of against our restatement alone.  __graft_entry__.build() builds it where the
+reference exists; the binary is git-ignored (oracle/_ref/) and travels to the GPU machine with the built tree; the vectors it produced are
+committed under tests/golden/ (make_refpin_golden.py).
 -ffp-contract=off: the stand-in for pcl::transformPointCloud states PCL's unfused mul / add order."""
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = "/root/reference"
 UNITS = ["src/hdl_graph_slam/information_matrix_calculator.cpp", "src/hdl_graph_slam/keyframe.cpp"]
 HEADERS = ["include/hdl_graph_slam/information_matrix_calculator.hpp", "include/hdl_graph_slam/keyframe.hpp"]
-OUT = os.path.join(ROOT, "tests", "_refpin")
+OUT = os.path.join(ROOT, "oracle", "_ref", "refpin")
 DRIVER = os.path.join(ROOT, "tests", "cpp", "refpin_main.cpp")
 
 

@@ -31,7 +31,7 @@
 #include <hdl_graph_slam/information_matrix_calculator.hpp>
 #include <hdl_graph_slam/map_cloud_generator.hpp>
 #include <resident_clouds_hip.hpp>
-// the unpatched translation units are linked in under other class names (tests/integration_build.py): declare those classes from the same headers
+// the unpatched translation units are linked in under other class names (oracle/integration_build.py): declare those classes from the same headers
 #undef INFORMATION_MATRIX_CALCULATOR_HPP
 #define InformationMatrixCalculator InformationMatrixCalculatorCPU
 #include <hdl_graph_slam/information_matrix_calculator.hpp>

@@ -1,4 +1,4 @@
-// TEST ONLY — the PATCHED apps/prefiltering_nodelet.cpp (integration/hdl_graph_slam_hip.patch applied to a scratch copy; tests/integration_build.py) is
+// TEST ONLY — the PATCHED apps/prefiltering_nodelet.cpp (integration/hdl_graph_slam_hip.patch applied to a scratch copy; oracle/integration_build.py) is
 // included as it is: the nodelet class lives in that .cpp.  The stand-in ROS graph (tests/mock_ros/ros/ros.h) hands the test the callback the nodelet
 // subscribed with and the clouds it published, so the reference's own PrefilteringNodelet::onInit / initialize_params / cloud_callback RUN:
 //   prefilter_nodelet_main <cloud.bin> <out_device.bin> <out_cpu.bin> [rosparam=value ...]

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE — "reference code run here".  Driver around two UNMODIFIED reference translation units,
 //   /root/reference/src/hdl_graph_slam/information_matrix_calculator.cpp   (calc_fitness_score :49-80, calc_information_matrix :25-47)
 //   /root/reference/src/hdl_graph_slam/keyframe.cpp                        (KeyFrame::save :21-58, KeyFrame::load :60-145)
-// compiled where they lie (tests/refpin_build.py) against the stand-in ROS / PCL / Eigen / g2o / boost headers of tests/mock_*.
+// compiled where they lie (oracle/refpin_build.py) against the stand-in ROS / PCL / Eigen / g2o / boost headers of tests/mock_*.
 // What this pins is the arithmetic and the text format those two files contain themselves: the loop, the `nn_dists[0] <= max_range`
 // comparison of a SQUARED distance, the double accumulation, the DBL_MAX return, the weight() curve, the token stream of `data`.
 // What stays ours: the kd-tree (exact, like FLANN's at eps = 0), pcl::transformPointCloud's order of operations (pcl/common/transforms.h in

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/refpin_v1.npz and tests/golden/refpin_keyframes/ — vectors produced by REFERENCE CODE RUN HERE: the unmodified
 src/hdl_graph_slam/information_matrix_calculator.cpp and src/hdl_graph_slam/keyframe.cpp of /root/reference, compiled against tests/mock_*
-(tests/refpin_build.py, tests/cpp/refpin_main.cpp).  Needs /root/reference (the build container); the GPU box only reads the committed vectors.
+(oracle/refpin_build.py, tests/cpp/refpin_main.cpp).  Needs /root/reference (the build container); the GPU box only reads the committed vectors.
 
     fit_*      calc_fitness_score (:49-80) on committed clouds (tests/golden/vlp16_pair_seed1.npz, vlp16_next_rows_v3.npz) at several poses and
                max_range values incl. the declaration's default (DBL_MAX), the squared-vs-unsquared comparison (1.0 vs 0.25), a range with no
@@ -22,7 +22,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 import refpin_build as RB  # noqa: E402
 from hdl_graph_slam_amd import synth, keyframe_io as K  # noqa: E402
 

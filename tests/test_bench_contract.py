@@ -77,17 +77,23 @@ def test_single_rank_line():
         assert c["gpu_over_cpu"]["ratio"] > 0 and "whole" not in c["gpu_over_cpu"]["against"] or True
 
 
-def test_two_ranks_through_torch_distributed_run():
+def test_two_ranks_through_torch_distributed_run(tmp_path):
     """The N > 1 path exactly as the driver launches it: rank/world from the environment, the records all-gathered, the time
-    max-reduced over ranks, one line from rank 0, cpu_baseline null."""
+    max-reduced over ranks, one line from rank 0, cpu_baseline null; --dump-outputs holds the records of ALL candidates, as the
+    caller of the sharded path receives them."""
+    import numpy as np
     import socket
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", *SMALL, "--method", "NDT_OMP", "--ndt-line-search", "--strong-candidates", "4"])
+                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", *SMALL, "--method", "NDT_OMP", "--ndt-line-search", "--strong-candidates", "4",
+                "--dump-outputs", str(tmp_path)])
     _check(rec, 2, 2, 1, 2)
+    out = _load_dump(tmp_path)
+    assert out["final_transformation"].shape == (4, 16) and np.array_equal(out["candidate_id"], np.arange(4))
+    assert int(out["best_candidate"][0]) == rec["best_candidate"]
     st = rec["config4_strong_scaling"]     # BASELINE config 4 next to the weak line (512 candidates in total on the device; 4 here)
     assert st["scaling"] == "strong" and st["candidates_total"] == 4 and st["candidates_per_gpu"] == 2 and len(st["per_rank_ms_per_step"]) == 2
     assert "More-Thuente" in rec["config"]["workload"] and rec["mean_linearizations"] >= rec["mean_iterations"] + 1
@@ -153,3 +159,44 @@ def test_single_process_mode_drives_one_engine_per_gpu_from_threads():
     rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--config", "4", "--steps", "2", "--warmup", "1", "--candidates", "3", "--distinct", "2",
                 "--sensor", "VLP-16", "--downsample", "0.5"])
     assert rec["scaling"] == "strong" and rec["config"]["candidates_total"] == 3
+
+
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+@pytest.mark.parametrize("config,extra", [(0, [*SMALL, "--no-ndt-record", "--no-plane-record"]), (2, ["--sensor", "VLP-16", "--downsample", "0.5"]),
+                                          (3, ["--sensor", "VLP-16", "--downsample", "0.5", "--speed", "2", "--no-adapter-record", "--no-kitti-records",
+                                               "--oracle-sweeps", "0"])])
+def test_dump_outputs_writes_the_last_timed_step(config, extra, tmp_path):
+    """--dump-outputs DIR: the primary record's last timed step as DIR/<name>.npy (float32 / float64 only), the same arrays on a second run with the same
+    arguments (seeded inputs), and nothing of it in the JSON line."""
+    import numpy as np
+    dumps = []
+    for run in range(1 if config == 2 else 2):
+        d = tmp_path / f"run{run}"
+        rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", str(config), *extra,
+                    "--seeds", "1", "--no-cpu-baseline", "--dump-outputs", str(d)])
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and "_last_step" not in rec
+        dumps.append(_load_dump(d))
+    out = dumps[0]
+    assert {"final_transformation", "converged", "iterations", "fitness_score", "num_inliers", "lm_tries"} <= set(out)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    n = 2 if config == 0 else 1
+    assert out["final_transformation"].shape == (n, 16) and out["iterations"].shape == (n,)
+    if len(dumps) == 2:
+        assert set(out) == set(dumps[1])
+        for k in out:
+            assert np.array_equal(out[k], dumps[1][k], equal_nan=True), k   # a single align leaves fitness_score NaN (not evaluated)
+    if config == 0:
+        assert int(out["best_candidate"][0]) == rec["best_candidate"] and float(np.mean(out["iterations"])) == rec["mean_iterations"]
+    if config == 2:
+        assert int(out["iterations"][0]) == rec["iterations"] and int(out["converged"][0]) == rec["converged"]
+    if config == 3:
+        assert out["odom"].shape == (4, 4) and out["odom"].dtype == np.float32
+        # the stream stays within the first keyframe (5 m rule, 0.2 m per sweep): keyframe_pose is the identity, so matching() returned the
+        # converged registration's own final_transformation (column-major in the record)
+        assert int(out["converged"][0]) == 1
+        assert np.array_equal(out["odom"], out["final_transformation"][0].reshape(4, 4).T)

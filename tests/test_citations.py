@@ -1,13 +1,17 @@
 """Every `file:line` citation of the reference in the interface header, the adapters, the host mirrors and the documents points
-at an existing file of /root/reference with at least that many lines.  Skipped where the reference is absent (the GPU box)."""
+at an existing file of the reference with at least that many lines.  The files and their lengths come from tests/golden/reference_line_counts.json
+(tests/golden/make_reference_line_counts.py), which is checked against the reference tree wherever that tree is present."""
 import glob
+import json
 import os
 import re
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
+LINE_COUNTS = os.path.join(ROOT, "tests", "golden", "reference_line_counts.json")
 CITE = re.compile(r"(?<![\w/.])((?:[\w.-]+/)*[\w.-]+\.(?:cpp|hpp|launch|xml|txt))`?:(\d+)(?:[-–](\d+))?")
 
 
@@ -17,12 +21,23 @@ def _sources():
     return sorted(f for p in pats for f in glob.glob(os.path.join(ROOT, p)))
 
 
+def _line_counts():
+    with open(LINE_COUNTS) as fh:
+        return json.load(fh)
+
+
 @pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is not present here")
+def test_committed_line_counts_match_the_reference_tree():
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_reference_line_counts as MC
+    assert MC.line_counts(REF) == _line_counts()
+
+
 def test_reference_citations_resolve():
+    counts = _line_counts()
     index = {}
-    for d, _, files in os.walk(REF):
-        for f in files:
-            index.setdefault(f, []).append(os.path.join(d, f))
+    for rel in counts:
+        index.setdefault(os.path.basename(rel), []).append("/" + rel)
     own = {os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "**", "*"), recursive=True)}
     checked, bad = 0, []
     for src in _sources():
@@ -36,7 +51,7 @@ def test_reference_citations_resolve():
                     continue            # a citation of this repository's own files, or of a third-party file named in prose
                 bad.append((os.path.relpath(src, ROOT), m.group(0), "no such path in the reference"))
                 continue
-            n_lines = max(sum(1 for _ in open(c, errors="replace")) for c in cands)
+            n_lines = max(counts[c[1:]] for c in cands)
             checked += 1
             if hi < lo or hi > n_lines:
                 bad.append((os.path.relpath(src, ROOT), m.group(0), f"file has {n_lines} lines"))

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import integration_build as IB  # noqa: E402
 
 needs_reference = pytest.mark.skipif(not IB.have_reference(), reason="the reference tree (/root/reference) is only present in the build container")
@@ -154,7 +154,7 @@ def test_patched_factory_and_loop_detector_run_on_the_emulated_kernels(tmp_path)
 @pytest.mark.gpu
 def test_patched_factory_and_loop_detector_on_the_gpu(tmp_path):
     exe = IB.build("hip")
-    assert exe is not None and os.path.exists(exe), "integration/_build/integration_main is built by __graft_entry__.build() where /root/reference exists"
+    assert exe is not None and os.path.exists(exe), "oracle/_ref/integration/integration_main is built by __graft_entry__.build() where /root/reference exists"
     from hdl_graph_slam_amd import _lib as L
     from hdl_graph_slam_amd.registration import RegistrationHIP
     from hdl_graph_slam_amd.registrations import select_registration_method

@@ -2,7 +2,7 @@
 
 The engines of this path (ndt_omp, fast_gicp, PCL) are not under /root/reference and cannot be built in this image, so most parity statements of
 this repository read "against our restatement".  Two pieces of the path DO live in the reference tree, and their translation units compile
-UNMODIFIED against the stand-in headers of tests/mock_* (tests/refpin_build.py):
+UNMODIFIED against the stand-in headers of tests/mock_* (oracle/refpin_build.py):
 
   * src/hdl_graph_slam/information_matrix_calculator.cpp — calc_fitness_score (:49-80), the in-tree statement of pcl::Registration::getFitnessScore
     (rows a4 / a10 / f1), and calc_information_matrix (:25-47);
@@ -40,7 +40,7 @@ DBL_MAX = float(np.finfo(np.float64).max)
 FIT_RTOL = 2e-6      # measured: oracle 1.2e-7 (the two PCL orders differ from each other by 2.8e-7)
 
 needs_reference = pytest.mark.skipif(not RB.have_reference(), reason="the reference tree (/root/reference) is only present in the build container")
-needs_binary = pytest.mark.skipif(not RB.have_reference() and not os.path.exists(RB.exe()), reason="tests/_refpin/refpin_main is built where /root/reference exists")
+needs_binary = pytest.mark.skipif(not RB.have_reference() and not os.path.exists(RB.exe()), reason="oracle/_ref/refpin/refpin_main is built where /root/reference exists")
 
 
 @pytest.fixture(scope="module")
