@@ -1,7 +1,7 @@
 // registration_hip.hpp — header-only pcl::Registration adapter over the C-ABI of include/hgs_registration.h.
 //
 // This is the object hdl_graph_slam::select_registration_method (src/hdl_graph_slam/registrations.cpp:22-124) returns for
-// the new registration_method values "FAST_GICP_HIP", "FAST_VGICP_HIP" and "NDT_HIP" (see INTEGRATION.md for the patch).
+// the new registration_method values "FAST_GICP_HIP", "FAST_VGICP_HIP", "NDT_HIP" and "ICP_HIP" (see INTEGRATION.md for the patch).
 // The nodelets keep calling the pcl::Registration surface they already use:
 //     setInputTarget / setInputSource / align / hasConverged / getFinalTransformation / getFitnessScore /
 //     getSearchMethodTarget()->nearestKSearch
@@ -111,9 +111,11 @@ public:
   using Ptr = boost::shared_ptr<RegistrationHIP<PointSource, PointTarget>>;
 #endif
 
-  // `method`: HGS_FAST_GICP / HGS_FAST_VGICP / HGS_NDT_OMP.  Parameters start at the factory defaults of registrations.cpp.
+  // `method`: HGS_FAST_GICP / HGS_FAST_VGICP / HGS_NDT_OMP / HGS_ICP.  Parameters start at the factory defaults of registrations.cpp.
   explicit RegistrationHIP(int method, int device_id = 0) {
-    this->reg_name_ = method == HGS_NDT_OMP ? "hgs_hip::NDT" : (method == HGS_FAST_VGICP ? "hgs_hip::FastVGICP" : "hgs_hip::FastGICP");
+    this->reg_name_ = method == HGS_NDT_OMP ? "hgs_hip::NDT"
+                      : method == HGS_FAST_VGICP ? "hgs_hip::FastVGICP"
+                      : method == HGS_ICP ? "hgs_hip::ICP" : "hgs_hip::FastGICP";
     if (hgs_params_default(method, &params_) != HGS_OK) throw std::invalid_argument("RegistrationHIP: unknown method");
     params_.device_id = device_id;
     lazy_tree_.reset(new LazyKdTree<PointTarget>());
@@ -137,6 +139,8 @@ public:
   void setResolution(double r) { params_.resolution = r; recreate(); }
   void setNeighborhoodSearchMethod(int hgs_neighbor_search_value) { params_.neighbor_search = hgs_neighbor_search_value; recreate(); }
   void setRotationEpsilon(double eps) { params_.rotation_epsilon = eps; recreate(); }
+  // pcl::IterativeClosestPoint::setUseReciprocalCorrespondences (registrations.cpp:63); ICP only
+  void setUseReciprocalCorrespondences(bool on) { params_.icp_reciprocal = on ? 1 : 0; recreate(); }
   // extension: 1 = a working More-Thuente line search in NDT (ndt_omp itself never runs its loop; 0 reproduces it)
   void setNdtLineSearch(bool on) { params_.ndt_line_search = on ? 1 : 0; recreate(); }
   // fast_gicp::FastGICP::setRegularizationMethod (hgs_regularization value); never called by hdl_graph_slam

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhgs_hip.so")
 
 HGS_OK = 0
 HGS_ERR_INVALID_ARGUMENT, HGS_ERR_NO_TARGET, HGS_ERR_NO_SOURCE, HGS_ERR_HIP, HGS_ERR_NO_DEVICE, HGS_ERR_UNSUPPORTED, HGS_ERR_OUT_OF_MEMORY, HGS_ERR_INTERNAL, HGS_ERR_COMM = range(1, 10)
-HGS_FAST_GICP, HGS_FAST_VGICP, HGS_NDT_OMP = 0, 1, 2
+HGS_FAST_GICP, HGS_FAST_VGICP, HGS_NDT_OMP, HGS_ICP = 0, 1, 2, 3
 HGS_KDTREE, HGS_DIRECT1, HGS_DIRECT7, HGS_DIRECT27 = 0, 1, 2, 3
 HGS_REG_FROBENIUS, HGS_REG_PLANE, HGS_REG_MIN_EIG, HGS_REG_NORMALIZED_MIN_EIG, HGS_REG_NONE = 0, 1, 2, 3, 4
 STAGES = ["upload", "index", "covariance", "voxelize", "linearize", "error", "solve", "fitness", "prefilter"]
@@ -36,6 +36,16 @@ class HgsParams(C.Structure):
         ("device_id", C.c_int32), ("regularization_method", C.c_int32),
         ("ndt_line_search", C.c_int32), ("reserved", C.c_int32),
     ]
+
+    # The last slot is hgs_params.icp_reciprocal in the header; it keeps its old field name here so that the layout stays
+    # comparable field by field with the oracle's copy of the struct.
+    @property
+    def use_reciprocal_correspondences(self) -> bool:
+        return bool(self.reserved)
+
+    @use_reciprocal_correspondences.setter
+    def use_reciprocal_correspondences(self, on: bool) -> None:
+        self.reserved = 1 if on else 0
 
 
 class HgsPrefilterParams(C.Structure):
@@ -78,7 +88,7 @@ EXPORTS = [
     "hgs_comm_get_unique_id", "hgs_comm_init", "hgs_comm_finalize", "hgs_loop_match_batch_sharded",
     "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_cloud_download", "hgs_map_cloud_generate",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
-    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_ndt_cells", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
+    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_ndt_cells", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
 ]
 
 _lib = None
@@ -131,6 +141,7 @@ def lib():
     L.hgs_debug_target_covariances.argtypes = [vp, vp]
     L.hgs_debug_set_option.argtypes = [vp, C.c_char_p, C.c_int32]
     L.hgs_debug_gicp_linearize.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.hgs_debug_icp_correspond.argtypes = [vp, vp, vp, vp]
     L.hgs_debug_ndt_cells.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     L.hgs_debug_ndt_derivatives.argtypes = [vp, vp, vp, vp, vp]
     L.hgs_debug_merge_shard_records.argtypes = [vp, vp, C.c_int32, C.c_size_t, C.c_size_t, vp, vp]

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hgs_gicp.h"
+#include "hgs_icp.h"
 #include "hgs_ndt.h"
 #include "hgs_vgicp.h"
 
@@ -122,6 +123,12 @@ void launch_gicp_error_round2(hipStream_t s, const CloudDesc* descs, TargetView 
                               double* partials_err, int max_blocks, int err_blocks /* grid */, int B, int lin_tile_points);
 void launch_gicp_decide(hipStream_t s, const CloudDesc* descs, GicpState* states, GicpConsts c, const double* partials_err, int max_blocks, int B, Progress prog);
 void launch_gicp_results(hipStream_t s, const GicpState* states, DevResult* out, int B);
+
+// point-to-point ICP (hgs_icp.h): one correspondence pass + one control step per round, the source read in its Hilbert order
+void launch_icp_init(hipStream_t s, IcpState* states, const float* guesses, int B, Progress prog);
+void launch_icp_correspond(hipStream_t s, const CloudDesc* descs, TargetView tgt, const IcpState* states, IcpConsts c, double* partials, int max_blocks, int B);
+void launch_icp_solve(hipStream_t s, const CloudDesc* descs, IcpState* states, IcpConsts c, const double* partials, int max_blocks, int B, Progress prog);
+void launch_icp_results(hipStream_t s, const IcpState* states, DevResult* out, int B);
 
 void launch_fitness(hipStream_t s, const CloudDesc* descs, TargetView tgt, const DevResult* poses, double max_range, double* partials, int max_blocks, int B,
                     int use_seed, int qpw);

@@ -910,6 +910,20 @@ GicpConsts gicp_consts(const hgs_params& p) {
   return c;
 }
 
+// pcl::IterativeClosestPoint as registrations.cpp:57-64 configures it, with DefaultConvergenceCriteria's thresholds (hgs_icp.h)
+IcpConsts icp_consts(const hgs_params& p) {
+  IcpConsts c;
+  const double thr = p.max_correspondence_distance;
+  c.max_corr2 = thr * thr;
+  c.search_bound2 = c.max_corr2 >= (double)FLT_MAX ? FLT_MAX : nextafterf((float)c.max_corr2, FLT_MAX);
+  c.max_iterations = p.max_iterations;
+  c.trans_eps = p.transformation_epsilon;
+  c.rot_thr = p.rotation_epsilon > 0 ? p.rotation_epsilon : 1.0 - p.transformation_epsilon;
+  c.reciprocal = p.icp_reciprocal ? 1 : 0;
+  c.pad = 0;
+  return c;
+}
+
 NdtConsts ndt_consts(const hgs_params& p) {
   NdtConsts c;
   const double c1 = 10.0 * (1 - p.ndt_outlier_ratio);
@@ -1088,11 +1102,12 @@ void drive_lanes(std::vector<BatchLane>& lanes, long max_rounds, F&& enqueue_rou
 }
 
 // getFitnessScore of one lane's problems at the poses stored in h->results (exact 1-NN of every transformed source point
-// in the target; FAST_GICP seeds the search with the final correspondences).
+// in the target; FAST_GICP and ICP seed the search with the final correspondences).
+bool corr_seeds_fitness(int method) { return method == HGS_FAST_GICP || method == HGS_ICP; }
 void lane_fitness(hgs_handle* h, BatchLane& L, const CloudDesc* d_descs, double max_range, int max_blocks, int qpw, int nn_tile) {
   StageTimer tm(h, HGS_STAGE_FITNESS);
   DevResult* res = h->results.as<DevResult>() + L.b0;
-  launch_fitness(L.stream, d_descs + L.b0, target_view(h->target), res, max_range, L.partials_err, max_blocks, L.B, h->prm.method == HGS_FAST_GICP ? 1 : 0, qpw);
+  launch_fitness(L.stream, d_descs + L.b0, target_view(h->target), res, max_range, L.partials_err, max_blocks, L.B, corr_seeds_fitness(h->prm.method) ? 1 : 0, qpw);
   launch_fitness_final(L.stream, d_descs + L.b0, L.partials_err, max_blocks, res, L.B, nn_tile);
 }
 
@@ -1114,6 +1129,11 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
     all.push_back(tgt);
     HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
     if (method == HGS_FAST_VGICP) HGS_TRY(ensure_vgicp_target(h, tgt));
+  } else if (method == HGS_ICP) {
+    // the target's index always; the sources' too: k_icp_correspond reads them in Hilbert order (a wave's 64 queries are neighbours, and corr[]
+    // is indexed like GICP's, so the fitness pass can start from it) and the reciprocal search walks the source's own tree
+    all.push_back(tgt);
+    HGS_TRY(ensure_index(h, all));
   } else {
     HGS_TRY(ensure_ndt_target(h, tgt));
   }
@@ -1220,6 +1240,29 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
       HGS_HIP(h, hipEventRecord(h->early_event, h->stream));
       h->early_pending = true;
     }
+  } else if (method == HGS_ICP) {
+    // one correspondence pass + one control step per round: a registration takes at most max(1, max_iterations) rounds (+2 as the other methods)
+    const IcpConsts c = icp_consts(h->prm);
+    HGS_HIP(h, h->states.reserve((size_t)B * sizeof(IcpState)));
+    IcpState* st = h->states.as<IcpState>();
+    const TargetView tv = target_view(tgt);
+    const long max_rounds = (long)std::max(0, c.max_iterations) + 2;
+    std::vector<BatchLane> lanes;
+    HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccIcp * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, err_blocks));
+    auto finish_lane = [&](BatchLane& L) {
+      launch_icp_results(L.stream, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
+      if (fit_max_range) lane_fitness(h, L, d_descs, *fit_max_range, max_blocks, qpw, nn_tile);
+    };
+    for (BatchLane& L : lanes) launch_icp_init(L.stream, st + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, L.B, L.prog);
+    drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
+      {
+        StageTimer tm(h, HGS_STAGE_LINEARIZE);
+        launch_icp_correspond(L.stream, d_descs + L.b0, tv, st + L.b0, c, L.partials, max_blocks, L.B);
+      }
+      StageTimer tm(h, HGS_STAGE_SOLVE);
+      launch_icp_solve(L.stream, d_descs + L.b0, st + L.b0, c, L.partials, max_blocks, L.B, L.prog);
+    }, finish_lane);
+    HGS_TRY(close_lanes(h, lanes));
   } else {
     const NdtConsts c = ndt_consts(h->prm);
     HGS_HIP(h, h->states.reserve((size_t)B * sizeof(NdtState)));
@@ -1438,13 +1481,13 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
 }
 
 int hgs_params_default(int32_t method, hgs_params* p) try {
-  if (!p || method < HGS_FAST_GICP || method > HGS_NDT_OMP) return HGS_ERR_INVALID_ARGUMENT;
+  if (!p || method < HGS_FAST_GICP || method > HGS_ICP) return HGS_ERR_INVALID_ARGUMENT;
   std::memset(p, 0, sizeof(*p));
   p->method = method;
   p->max_iterations = 64;                 // reg_maximum_iterations            registrations.cpp:32,54,110
   p->transformation_epsilon = 0.01;       // reg_transformation_epsilon        registrations.cpp:31,53,109
-  p->rotation_epsilon = 2e-3;             // fast_gicp LsqRegistration default
-  p->max_correspondence_distance = method == HGS_FAST_GICP ? 2.5 : (double)FLT_MAX;  // registrations.cpp:33 (VGICP: not set)
+  p->rotation_epsilon = method == HGS_ICP ? 0.0 : 2e-3;  // fast_gicp LsqRegistration default; ICP: hdl never sets it (threshold 1 - transformation_epsilon)
+  p->max_correspondence_distance = method == HGS_FAST_GICP || method == HGS_ICP ? 2.5 : (double)FLT_MAX;  // registrations.cpp:33,61 (VGICP: not set)
   p->correspondence_randomness = 20;      // reg_correspondence_randomness     registrations.cpp:34,55
   p->neighbor_search = method == HGS_NDT_OMP ? HGS_DIRECT7 : HGS_DIRECT1;  // registrations.cpp:103
   p->resolution = method == HGS_NDT_OMP ? 0.5 : 1.0;                        // registrations.cpp:93 / :52
@@ -1457,6 +1500,7 @@ int hgs_params_default(int32_t method, hgs_params* p) try {
   p->device_id = 0;
   p->regularization_method = HGS_REG_FROBENIUS;  // fast_gicp constructor default; hdl never calls the setter
   p->ndt_line_search = 0;                        // ndt_omp as it runs
+  p->icp_reciprocal = 0;                         // reg_use_reciprocal_correspondences  registrations.cpp:63
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(nullptr);
@@ -1465,7 +1509,7 @@ int hgs_params_default(int32_t method, hgs_params* p) try {
 int hgs_create(const hgs_params* p, hgs_handle** out) try {
   if (!p || !out) return HGS_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (p->method < HGS_FAST_GICP || p->method > HGS_NDT_OMP || p->max_iterations < 0 || p->correspondence_randomness < 1 || p->correspondence_randomness > 64 /* k_knn_cov's largest list */ || !(p->resolution > 0) ||
+  if (p->method < HGS_FAST_GICP || p->method > HGS_ICP || p->max_iterations < 0 || p->correspondence_randomness < 1 || p->correspondence_randomness > 64 /* k_knn_cov's largest list */ || !(p->resolution > 0) ||
       p->regularization_method < HGS_REG_FROBENIUS || p->regularization_method > HGS_REG_NONE) {
     g_create_error = "invalid hgs_params";
     return HGS_ERR_INVALID_ARGUMENT;
@@ -1754,7 +1798,7 @@ int hgs_fitness(hgs_handle* h, const float T[16], double max_range, double* scor
   HGS_TRY(set_device(h));
   HGS_TRY(upload_pose_as_result(h, T));
   std::vector<hgs_cloud*> src{h->source};
-  HGS_TRY(run_fitness(h, src, max_range, h->prm.method == HGS_FAST_GICP));
+  HGS_TRY(run_fitness(h, src, max_range, corr_seeds_fitness(h->prm.method)));
   std::vector<DevResult> r;
   HGS_TRY(fetch_results(h, 1, r));
   *score = r[0].fit_count > 0 ? r[0].fit_sum / (double)r[0].fit_count : std::numeric_limits<double>::max();
@@ -2665,6 +2709,62 @@ int hgs_debug_gicp_linearize(hgs_handle* h, const double T12[12], double* H36, d
       const int j = dcorr[i];
       if (voxel) to = j;  // VGICP: number of voxel correspondences of that source point
       else if (j >= 0 && (size_t)j < t_slots) std::memcpy(&to, &tpts[j].w, 4);
+      if (so >= 0 && (size_t)so < s->n_input) corr[so] = to;
+    }
+  }
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17, int32_t* corr) try {
+  std::unique_lock<std::recursive_mutex> api_lock__;
+  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  if (!h || !T12 || !sums17) return HGS_ERR_INVALID_ARGUMENT;
+  if (h->prm.method != HGS_ICP) return HGS_ERR_UNSUPPORTED;
+  if (!h->target) return HGS_ERR_NO_TARGET;
+  if (!h->source) return HGS_ERR_NO_SOURCE;
+  HGS_TRY(set_device(h));
+  hgs_cloud *s = h->source, *t = h->target;
+  std::vector<hgs_cloud*> all{s, t};
+  HGS_TRY(ensure_index(h, all));
+  const int max_blocks = std::max(1, ((int)s->n_input + kTileNN - 1) / kTileNN);
+  std::vector<hgs_cloud*> src{s};
+  const CloudDesc* d_descs = nullptr;
+  HGS_TRY(upload_descs(h, src, false, &d_descs, nullptr));
+  IcpState st;
+  for (int i = 0; i < 12; i++) st.x.m[i] = T12[i];
+  st.mse = st.mse_prev = DBL_MAX, st.phase = ICP_RUN, st.iterations = st.passes = st.converged = 0;
+  HGS_HIP(h, h->states.reserve(sizeof(IcpState)));
+  HGS_HIP(h, h->partials.reserve((size_t)max_blocks * kAccIcp * sizeof(double)));
+  HGS_HIP(h, hipMemcpyAsync(h->states.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+  launch_icp_correspond(h->stream, d_descs, target_view(t), h->states.as<IcpState>(), icp_consts(h->prm), h->partials.as<double>(), max_blocks, 1);
+  HGS_HIP(h, hipGetLastError());
+  std::vector<double> part((size_t)max_blocks * kAccIcp);
+  int s_nvalid = 0;
+  HGS_HIP(h, hipMemcpyAsync(&s_nvalid, &s->desc.meta->nvalid, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipMemcpyAsync(part.data(), h->partials.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  const size_t s_slots = (size_t)s->P * kLeaf, t_slots = (size_t)t->P * kLeaf;
+  std::vector<float4> spts, tpts;
+  std::vector<int> dcorr;
+  if (corr) {
+    spts.resize(s_slots), tpts.resize(t_slots), dcorr.resize(s_slots);
+    HGS_HIP(h, hipMemcpyAsync(spts.data(), s->desc.pts, s_slots * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    HGS_HIP(h, hipMemcpyAsync(tpts.data(), t->desc.pts, t_slots * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    HGS_HIP(h, hipMemcpyAsync(dcorr.data(), s->desc.corr, s_slots * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  }
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  const int ntiles = (s_nvalid + kTileNN - 1) / kTileNN;  // (the rows the pass wrote; the sums in tile order)
+  for (int k = 0; k < kAccIcp; k++) sums17[k] = 0.0;
+  for (int tile = 0; tile < ntiles && tile < max_blocks; tile++)
+    for (int k = 0; k < kAccIcp; k++) sums17[k] += part[(size_t)tile * kAccIcp + k];
+  if (corr) {
+    for (size_t i = 0; i < s->n_input; i++) corr[i] = -1;
+    for (int i = 0; i < s_nvalid && (size_t)i < s_slots; i++) {
+      int so, to = -1;
+      std::memcpy(&so, &spts[i].w, 4);
+      const int j = dcorr[i];
+      if (j >= 0 && (size_t)j < t_slots) std::memcpy(&to, &tpts[j].w, 4);
       if (so >= 0 && (size_t)so < s->n_input) corr[so] = to;
     }
   }

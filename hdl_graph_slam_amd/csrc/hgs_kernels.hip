@@ -1208,6 +1208,134 @@ void launch_gicp_results(hipStream_t s, const GicpState* states, DevResult* out,
   hipLaunchKernelGGL(k_gicp_results, dim3((B + 63) / 64), dim3(64), 0, s, states, out, B);
 }
 
+// ------------------------------------------------------------------------------------------------ ICP iteration
+// pcl::IterativeClosestPoint (registrations.cpp:57-64, hgs_icp.h): a round is one correspondence pass over the source in its Hilbert
+// order (k_icp_correspond, the 1-NN packet walk of k_gicp_linearize) and one control step per problem (k_icp_solve).  No covariances.
+__global__ void k_icp_init(IcpState* states, const float* guesses, int B, Progress prog) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b == 0) prog.dev[0] = 0, prog.dev[1] = 0;
+  if (b >= B) return;
+  icp_state_init(states[b], guesses + 16 * b);
+}
+void launch_icp_init(hipStream_t s, IcpState* states, const float* guesses, int B, Progress prog) {
+  hipLaunchKernelGGL(k_icp_init, dim3((B + 63) / 64), dim3(64), 0, s, states, guesses, B, prog);
+}
+
+// Per source point: exact 1-NN of the moved point in the target (seeded with the previous pass's correspondence), kept when
+// d2 <= max_corr^2 (PCL's test; k_gicp_linearize keeps fast_gicp's strict <); RECIPROCAL: the target point taken back into the source
+// frame must find this very point as its exact 1-NN in the source's own index, again within max_corr^2.  The 17 sums of the kept pairs
+// (hgs_icp.h kAccIcp) go through the wave sums and last_wave_stores into one partial row per 256-point tile; corr[] keeps the
+// correspondence (sorted target position or -1) as the next pass's seed and for the fitness pass.
+template <bool RECIPROCAL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_LINEARIZE_WAVES))) void k_icp_correspond(const CloudDesc* descs, TargetView tgt, const IcpState* states,
+                                                                                                       IcpConsts c, double* __restrict__ partials, int max_blocks) {
+  const int b = blockIdx.y;
+  if (states[b].phase != ICP_RUN) return;
+  const CloudDesc d = descs[b];
+  const int n = d.meta->nvalid;
+  constexpr int qpw = 64;
+  const int ntiles = (n + kTileNN - 1) / kTileNN;
+  const int tile = xcd_tile(blockIdx.x, ntiles);
+  if (tile >= ntiles) return;
+  __shared__ double lds[4 * kAccIcp];
+  __shared__ unsigned arrivals;
+  __shared__ __attribute__((aligned(512))) float park[kBlock / 64][kParkFloats];
+  if (threadIdx.x == 0) arrivals = 0u;
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const Pose T = states[b].x;
+  static_assert(kNW == 1 && kTileNN == (kBlock / 64) * qpw, "one packet of 64 consecutive source points per wave");
+  const int idx = tile * kTileNN + wave * qpw + (int)(threadIdx.x & 63);
+  const bool active = idx < n;
+  const float4 a = active ? load_stream(d.pts + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const F3 q = icp_move_point(T, a.x, a.y, a.z);
+  const int seed = active ? __builtin_nontemporal_load(d.corr + idx) : -1;  // (-1 / stale values only cost the walk time)
+  float d2;
+  int j, orig;
+  packet_nn1(view_of(tgt), park[wave], q, active, c.search_bound2, seed, qpw, d2, j, orig);
+  int jj = active ? j : -1;
+  if (jj >= 0 && !((double)d2 <= c.max_corr2)) jj = -1;
+  const float4 bp = jj >= 0 ? tgt.pts[jj] : make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (RECIPROCAL) {
+    const bool ractive = jj >= 0;
+    if (__ballot(ractive) != 0ull) {
+      const F3 r = icp_unmove_point(T, bp.x, bp.y, bp.z);
+      BvhView sv;
+      sv.nodes = d.nodes, sv.pts = d.pts, sv.lpts = d.lpts, sv.P = d.P, sv.n = n;
+      float rd2;
+      int rj, rorig;
+      packet_nn1(sv, park[wave], r, ractive, c.search_bound2, ractive ? idx : -1, qpw, rd2, rj, rorig);  // (seed: the point itself)
+      if (ractive && !(rj >= 0 && rorig == __float_as_int(a.w) && (double)rd2 <= c.max_corr2)) jj = -1;
+    }
+  }
+  if (active) __builtin_nontemporal_store(jj, d.corr + idx);
+  double acc[kAccIcp];
+  if (jj >= 0) {
+    icp_pair_terms(q, bp.x, bp.y, bp.z, d2, acc);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kAccIcp; k++) acc[k] = 0.0;
+  }
+  int lane;
+  HGS_LANE_ID(lane);
+  int slot[kAccIcp];
+#pragma unroll
+  for (int k = 0; k < kAccIcp; k++) slot[k] = k;
+  wave_sums_to<kAccIcp>(acc, slot, lds + wave * kAccIcp, lane);
+  last_wave_stores<kAccIcp>(lds, &arrivals, partials + ((size_t)b * max_blocks + tile) * kAccIcp, lane);
+}
+void launch_icp_correspond(hipStream_t s, const CloudDesc* descs, TargetView tgt, const IcpState* states, IcpConsts c, double* partials, int max_blocks, int B) {
+  if (c.reciprocal) hipLaunchKernelGGL(k_icp_correspond<true>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, states, c, partials, max_blocks);
+  else hipLaunchKernelGGL(k_icp_correspond<false>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, states, c, partials, max_blocks);
+}
+
+// One wave per problem: the tile partials added in a fixed order (lane l takes tiles l, l + 64, ...; then the wave sum) — the result
+// depends on the problem's own points only, not on lanes, batch or launch shape — then the Umeyama step and the convergence tests
+// on lane 0 (icp_after_pass), and the progress tick as k_gicp_decide gives it.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HGS_CONTROL_WAVES))) void k_icp_solve(const CloudDesc* descs, IcpState* states, IcpConsts c,
+                                                                                        const double* __restrict__ partials, int max_blocks, Progress prog) {
+  const int b = blockIdx.x;
+  bool finished_now = false;
+  if (HGS_CONTROL_PRIO) __builtin_amdgcn_s_setprio(HGS_CONTROL_PRIO);
+  if (states[b].phase == ICP_RUN) {  // (block-uniform)
+    const int ntiles = (descs[b].meta->nvalid + kTileNN - 1) / kTileNN;
+    const double* p = partials + (size_t)b * max_blocks * kAccIcp;
+    double s[kAccIcp];
+#pragma unroll
+    for (int k = 0; k < kAccIcp; k++) s[k] = 0.0;
+    for (int t = threadIdx.x; t < ntiles; t += 64)
+#pragma unroll
+      for (int k = 0; k < kAccIcp; k++) s[k] += p[(size_t)t * kAccIcp + k];
+#pragma unroll
+    for (int k = 0; k < kAccIcp; k++) s[k] = wave_sum(s[k]);
+    if (threadIdx.x == 0) {
+      IcpState st = states[b];
+      icp_after_pass(st, s, c);
+      states[b] = st;
+      finished_now = st.phase == ICP_DONE;
+    }
+  }
+  if (threadIdx.x == 0) progress_tick(prog, finished_now);
+}
+void launch_icp_solve(hipStream_t s, const CloudDesc* descs, IcpState* states, IcpConsts c, const double* partials, int max_blocks, int B, Progress prog) {
+  hipLaunchKernelGGL(k_icp_solve, dim3(B), dim3(64), 0, s, descs, states, c, partials, max_blocks, prog);
+}
+
+__global__ void k_icp_results(const IcpState* states, DevResult* out, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const IcpState st = states[b];
+  DevResult r;
+  pose_to_colmajor_f(st.x, r.T);
+  r.converged = st.converged, r.iterations = st.iterations, r.lm_tries = st.passes, r.pad = 0;
+  r.error = st.mse;
+  r.fit_sum = 0, r.fit_count = 0, r.pad2 = 0;
+  out[b] = r;
+}
+void launch_icp_results(hipStream_t s, const IcpState* states, DevResult* out, int B) {
+  hipLaunchKernelGGL(k_icp_results, dim3((B + 63) / 64), dim3(64), 0, s, states, out, B);
+}
+
 // ------------------------------------------------------------------------------------------------ fitness / NN queries
 // getFitnessScore: per source point exact (unbounded) 1-NN in the target; sum d2 over d2 <= max_range.
 // Algorithmic bytes per source point: 16 + 16 = 32.  Only the distance is needed: the quad walk runs without leaf / tie tracking.

@@ -274,6 +274,16 @@ class RegistrationHIP:
                                                      corr.ctypes.data_as(vp)))
         return H, b, float(e[0]), corr
 
+    def icp_correspond(self, T):
+        """One ICP correspondence pass at pose T: the 17 sums (pairs, sum p, sum q, sum q p^T row-major, sum d2) and, per source
+        point, the original index of its target point or -1."""
+        T12 = np.ascontiguousarray(np.asarray(T, np.float64)[:3, :4])
+        sums = np.zeros(17)
+        corr = np.empty(self._source_n, np.int32)
+        vp = C.c_void_p
+        self._check(L.lib().hgs_debug_icp_correspond(self._h, T12.ctypes.data_as(vp), sums.ctypes.data_as(vp), corr.ctypes.data_as(vp)))
+        return sums, corr
+
     def ndt_cells(self, cap: int = 1 << 20):
         ijk, mean, icov, npts = np.zeros((cap, 3), np.int32), np.zeros((cap, 3)), np.zeros((cap, 6), np.float32), np.zeros(cap, np.int32)
         n = C.c_int32()

@@ -14,6 +14,8 @@ from .registration import RegistrationHIP
 # reference routes by substring (registrations.cpp:57-99): "ICP" exactly -> pcl::IterativeClosestPoint; any other name containing
 # "GICP" -> pcl / pclomp GeneralizedIterativeClosestPoint; everything else -> NDT, pclomp's if the name contains "OMP", PCL's
 # single-threaded pcl::NormalDistributionsTransform (another algorithm: KDTREE neighbourhoods, its own line search) otherwise.
+# pcl::IterativeClosestPoint is rebuilt on the device under its own name, ICP_HIP (the convention of FAST_GICP_HIP / NDT_HIP): plain "ICP"
+# still names the CPU engine and is refused below.
 
 
 _REGULARIZATION = {"FROBENIUS": L.HGS_REG_FROBENIUS, "PLANE": L.HGS_REG_PLANE, "MIN_EIG": L.HGS_REG_MIN_EIG,
@@ -49,6 +51,13 @@ def params_from_rosparams(pnh) -> L.HgsParams:
         p.correspondence_randomness = int(get("reg_correspondence_randomness", 20))
         p.regularization_method = _regularization(pnh)
         return p
+    if method == "ICP_HIP":                                                         # registrations.cpp:57-64 (pcl::IterativeClosestPoint)
+        p = L.default_params(L.HGS_ICP)
+        p.transformation_epsilon = float(get("reg_transformation_epsilon", 0.01))
+        p.max_iterations = int(get("reg_maximum_iterations", 64))
+        p.max_correspondence_distance = float(get("reg_max_correspondence_distance", 2.5))
+        p.use_reciprocal_correspondences = get("reg_use_reciprocal_correspondences", False) in (True, 1, "1", "true", "True")
+        return p
     cpu_engine = None
     if method == "ICP":                                                             # registrations.cpp:57-64
         cpu_engine = "pcl::IterativeClosestPoint"
@@ -58,7 +67,7 @@ def params_from_rosparams(pnh) -> L.HgsParams:
         cpu_engine = "pcl::NormalDistributionsTransform"
     if cpu_engine is not None:
         raise NotImplementedError(f"registration_method={method}: the reference's factory builds {cpu_engine} for this name, a CPU engine this backend "
-                                  "does not replace (it implements FAST_GICP, FAST_VGICP and NDT_OMP); running the device NDT_OMP instead would change the result silently")
+                                  "does not replace (it implements FAST_GICP, FAST_VGICP, NDT_OMP and, as ICP_HIP, ICP); running the device NDT_OMP instead would change the result silently")
     if "NDT" not in method:                                                         # registrations.cpp:88-91 (then "... _OMP": pclomp's NDT)
         print(f"warning: unknown registration type({method})\n       : use NDT", file=sys.stderr)
     p = L.default_params(L.HGS_NDT_OMP)                                             # registrations.cpp:93,101-120

@@ -50,7 +50,8 @@ enum hgs_status {
 enum hgs_method {
   HGS_FAST_GICP = 0,  /* fast_gicp::FastGICP      — registrations.cpp:27-36   */
   HGS_FAST_VGICP = 1, /* fast_gicp::FastVGICP     — registrations.cpp:48-56   */
-  HGS_NDT_OMP = 2     /* pclomp::NormalDistributionsTransform — registrations.cpp:101-120 */
+  HGS_NDT_OMP = 2,    /* pclomp::NormalDistributionsTransform — registrations.cpp:101-120 */
+  HGS_ICP = 3         /* pcl::IterativeClosestPoint (point-to-point) — registrations.cpp:57-64; name "ICP_HIP" */
 };
 
 /* reg_nn_search_method (registrations.cpp:103,112-118) / FastVGICP neighbour search. */
@@ -76,8 +77,9 @@ typedef struct hgs_params {
   int32_t method;                     /* hgs_method                                                        */
   int32_t max_iterations;             /* reg_maximum_iterations           (64)                             */
   double transformation_epsilon;      /* reg_transformation_epsilon       (0.01)                           */
-  double rotation_epsilon;            /* fast_gicp LsqRegistration        (2e-3), not exposed by hdl       */
-  double max_correspondence_distance; /* reg_max_correspondence_distance  (2.5), FAST_GICP only            */
+  double rotation_epsilon;            /* fast_gicp LsqRegistration        (2e-3), not exposed by hdl; ICP (0):
+                                         cos(angle) threshold if > 0, else 1 - transformation_epsilon           */
+  double max_correspondence_distance; /* reg_max_correspondence_distance  (2.5), FAST_GICP / ICP            */
   int32_t correspondence_randomness;  /* reg_correspondence_randomness    (20) = k of the covariance kNN, 1..64 */
   int32_t neighbor_search;            /* hgs_neighbor_search: NDT (DIRECT7), VGICP (DIRECT1)               */
   double resolution;                  /* reg_resolution                   (NDT 0.5 / VGICP 1.0)            */
@@ -92,18 +94,19 @@ typedef struct hgs_params {
   int32_t ndt_line_search;            /* 0: ndt_omp as it runs (its More-Thuente loop never executes: every step is the
                                          Newton direction with length clamp(|dp|, eps/2, step_size)); 1: a working
                                          More-Thuente search (<= 10 trials, mu 1e-4, nu 0.9) — NOT the reference's result  */
-  int32_t reserved;
+  int32_t icp_reciprocal;             /* reg_use_reciprocal_correspondences (false), ICP only (was `reserved`, always 0) */
 } hgs_params;
 
 typedef struct hgs_result {
   float final_transformation[16]; /* getFinalTransformation(), column-major                                    */
   int32_t converged;              /* hasConverged()                                                            */
   int32_t iterations;             /* outer iterations executed                                                 */
-  double error;                   /* GICP/VGICP: last accepted sum e^T M e; NDT: trans_probability (score/N)  */
+  double error;                   /* GICP/VGICP: last accepted sum e^T M e; NDT: trans_probability (score/N);
+                                     ICP: mean d2 of the last iteration's correspondences (DBL_MAX: none)     */
   double fitness_score;           /* getFitnessScore(max_range) — filled by the batch entry point, else NaN    */
   uint32_t num_inliers;           /* #source points with d2 <= max_range in that score                         */
   int32_t candidate_id;           /* index into the caller's candidate list (batch), else 0                    */
-  int32_t lm_tries;               /* GICP: total LM tries; NDT: derivative passes                              */
+  int32_t lm_tries;               /* GICP: total LM tries; NDT: derivative passes; ICP: correspondence passes  */
   int32_t reserved;
 } hgs_result;
 
@@ -262,9 +265,9 @@ enum hgs_stage {
   HGS_STAGE_INDEX = 1,      /* spatial sort + bounding-interval tree build           */
   HGS_STAGE_COVARIANCE = 2, /* kNN covariance pre-pass (GICP/VGICP)                  */
   HGS_STAGE_VOXELIZE = 3,   /* Gaussian voxel table build (NDT / VGICP)              */
-  HGS_STAGE_LINEARIZE = 4,  /* correspondence search + J^T M J accumulation (GICP) / NDT derivatives */
+  HGS_STAGE_LINEARIZE = 4,  /* correspondence search + J^T M J accumulation (GICP) / NDT derivatives / ICP correspondence pass */
   HGS_STAGE_ERROR = 5,      /* LM trial error evaluation                             */
-  HGS_STAGE_SOLVE = 6,      /* 6x6 reductions + solve + LM/Newton update             */
+  HGS_STAGE_SOLVE = 6,      /* 6x6 reductions + solve + LM/Newton update (ICP: Umeyama step) */
   HGS_STAGE_FITNESS = 7,    /* fitness score NN pass                                 */
   HGS_STAGE_PREFILTER = 8,  /* distance filter + voxel grid + outlier removal        */
   HGS_STAGE_COUNT = 9
@@ -282,6 +285,10 @@ int hgs_debug_target_covariances(hgs_handle* h, float* out6);
 /* One fused correspondence + linearisation pass at pose T (double, row-major 3x4): H[36] row-major, b[6], sum of
  * errors, and per source point (original order) the original target index of its correspondence or -1. */
 int hgs_debug_gicp_linearize(hgs_handle* h, const double T12[12], double* H36, double* b6, double* err, int32_t* corr);
+/* ICP: one correspondence pass at pose T (double, row-major 3x4) with the engine's max_correspondence_distance and
+ * icp_reciprocal: sums17 = [pairs, sum p (3), sum q (3), sum q p^T (9, row-major), sum d2] over the kept pairs (p the moved source
+ * point as searched, q its target point), and per source point (original order) the original target index of its pair or -1. */
+int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17, int32_t* corr);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
 /* One NDT derivative pass at p = (tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */
