@@ -16,6 +16,15 @@ getFitnessScore for each.  Inputs are resident in HBM before the timed region.  
   5  1 M-point dense cloud, FAST_GICP, single align with the per-stage roofline
 --method NDT_OMP / FAST_VGICP switch the engine of the default workload and of config 4.
 
+A plain run does what the headline figure needs and nothing else: it builds the seeded inputs, warms up, times the steps, writes --dump-outputs and prints
+the line; the fields that belong to the other measurements are null in it.  --full adds, after the timed region and never inside it, everything else the
+benchmark measures or checks: the CPU baselines and the oracle's check of every timed record, the roofline (profiled steps of their own), the resident /
+warm variants, the other scene seeds and every sub-record (fast_gicp_plane, ndt_omp, r02_candidate_set, config4_strong_scaling, config 3's at_8_mps,
+adapter_path and KITTI pipelines).  The --no-* switches and the options that size those measurements act under --full only.
+
+Every run ray-casts its inputs itself, on up to 16 host threads: the scan cache of hdl_graph_slam_amd.synth is switched off here, so that no run depends
+on files an earlier run left behind.
+
 One JSON line on rank 0:  value = units/sec over all ranks (whole job)."""
 from __future__ import annotations
 
@@ -185,12 +194,17 @@ def main():
                     "to its caller (a sharded batch: the records of ALL candidates) as DIR/<name>.npy (float32 / float64), for output-for-output "
                     "comparison of two builds on the same seeded inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything else the benchmark measures or checks: CPU baselines and the oracle's check "
+                    "of the timed records, roofline, resident / warm variants, the other scene seeds, the sub-records (other engines, candidate sets, speeds, pipelines). "
+                    "Off by default: a plain run sets up, warms up, times the steps and prints the line, with those fields null")
     ap.add_argument("--cpu-sample", type=int, default=3, help="units registered by the CPU oracle for cpu_baseline")
     args = ap.parse_args()
 
     # the CPU legs run the OpenMP oracle in this process: idle OpenMP workers must sleep, not spin, or they compete with the host
     # thread that keeps the GPU's queues filled in the GPU measurements that follow (NDT sub-record, continuity record, other seeds)
     os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
+    # every run casts its own scans: nothing is read from, or left in, the per-user scan cache of hdl_graph_slam_amd.synth
+    os.environ["HGS_SCAN_CACHE"] = ""
     # this process creates up to four engines one after the other: 8 hardware queues keep a later engine's lanes on queues of their own.  The LAUNCHER sets
     # it (here; a launch file in a deployment) — the library itself never touches the environment; it only counts its streams against this budget
     rank = int(os.environ.get("RANK", "0"))
@@ -238,7 +252,8 @@ def main():
     ctx = dict(args=args, rank=rank, local_rank=local_rank, world=world, torch=torch, emulated=emulated, dist=dist, coll_device=coll_device, sharded=sharded,
                synth=synth, workloads=workloads, L=L, select_registration_method=select_registration_method, select_best=select_best, CandidateShard=CandidateShard)
     n_seeds = args.seeds if args.seeds >= 0 else (3 if world == 1 and not emulated else 1)
-    ctx["n_seeds"] = max(1, n_seeds)
+    ctx["n_seeds"] = max(1, n_seeds) if args.full else 1
+    ctx["cast_workers"] = max(1, min(16, os.cpu_count() or 1))   # host threads that ray-cast the inputs (the scans are the same for every count)
     if args.config in (0, 4):
         out = run_loop_batch(ctx)
     elif args.config in (2, 5):
@@ -302,7 +317,7 @@ def base_line(ctx, value, unit, steps, dt, dtype, workload, extra_config):
     a = ctx["args"]
     return {"metric": "registrations/sec (64-beam ~120k-pt pair), loop-closure batch" if a.config == 0 else "registrations/sec", "value": round(value, 3), "unit": unit,
             "n_gpus": ctx["world"], "steps": steps, "warmup": a.warmup, "ms_per_step": round(dt / max(steps, 1) * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": dtype,
+            "scaling": "weak", "vs_baseline": None, "dtype": dtype, "full": bool(a.full),
             "data": "synthetic" if not ctx["emulated"] else "synthetic (EMULATED ON THE CPU - not a measurement)",
             "config": dict({"workload": workload, "baseline_config": a.config if a.config else "metric (config 3's scan size in config 4's batch shape)"}, **extra_config)}
 
@@ -340,7 +355,7 @@ def dump_outputs(directory, arrays):
 # ============================================================================================== loop-closure batch (default, config 4)
 def run_loop_batch(ctx):
     """The metric's configuration (default) and config 4.  One engine per method; the primary method's line is the JSON line, and on
-    the default command (FAST_GICP, N = 1) the factory-default engine NDT_OMP (src/hdl_graph_slam/registrations.cpp:26,101-120) is
+    the default command with --full (FAST_GICP, N = 1) the factory-default engine NDT_OMP (src/hdl_graph_slam/registrations.cpp:26,101-120) is
     measured on the same candidate set right after it and reported as the `ndt_omp` sub-record."""
     a, rank, world = ctx["args"], ctx["rank"], ctx["world"]
     cfg4 = a.config == 4
@@ -349,7 +364,9 @@ def run_loop_batch(ctx):
     steps = a.steps or (16 if cfg4 else 64)   # >= 1 s of timed region at the measured 62 / 16 ms per step
     if a.single_process:
         return measure_single_process(ctx, method, B, steps)
-    out = measure_loop_batch(ctx, method, B, steps, ctx["n_seeds"], with_cpu=not a.no_cpu_baseline, with_resident=True, max_range=None)
+    out = measure_loop_batch(ctx, method, B, steps, ctx["n_seeds"], with_cpu=a.full and not a.no_cpu_baseline, with_resident=a.full, max_range=None)
+    if not a.full:
+        return out   # a plain run ends with the primary record's timed region
     if a.config == 0 and world > 1 and not a.no_strong_record:
         # next to the weak line (64 candidates per GPU): BASELINE config 4 — 1 query x 512 HDL-32E candidates IN TOTAL, sharded over the ranks (strong scaling)
         a.config = 4
@@ -406,7 +423,7 @@ def measure_single_process(ctx, method, B, steps):
     set_kwargs = dict(ctx["workloads"].MILD_LOOP_SET) if a.mild_set else {}
     if a.distinct:
         set_kwargs["n_distinct"] = a.distinct
-    wl = ctx["workloads"].make_loop_closure_set(sensor, scene_seed=0, n_candidates=total, downsample=a.downsample or None,
+    wl = ctx["workloads"].make_loop_closure_set(sensor, scene_seed=0, n_candidates=total, downsample=a.downsample or None, workers=ctx["cast_workers"],
                                                 **dict(set_kwargs, n_distinct=min(set_kwargs.get("n_distinct", 16), total)))
     d_cands = [m.upload(i, c) for i, c in enumerate(wl.candidates)]
 
@@ -485,7 +502,7 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
 
     def load(seed):
         # every rank holds the query keyframe (replicated target) and its own shard of the N*B candidates
-        wl = ctx["workloads"].make_loop_closure_set(sensor, scene_seed=seed, n_candidates=B, downsample=a.downsample or None,
+        wl = ctx["workloads"].make_loop_closure_set(sensor, scene_seed=seed, n_candidates=B, downsample=a.downsample or None, workers=ctx["cast_workers"],
                                                     **dict(set_kwargs, n_distinct=min(set_kwargs.get("n_distinct", 16), B)))
         rng = np.random.default_rng(100 + rank)
         if rank > 0:  # different guesses per rank so that the shards are not identical problems
@@ -595,31 +612,33 @@ def measure_loop_batch(ctx, method, B, steps, n_seeds, with_cpu, with_resident, 
     rmse_r = float(np.sqrt(np.mean([e[1] ** 2 for e in et])))
     within = int(np.sum([e[0] < 0.3 and e[1] < 0.02 for e in et]))   # candidates that ended near their ground truth (GICP on raw rings: decimetres)
 
-    # ---- roofline of the dominant kernel: HIP events on the handle's stream around every launch of each stage
-    reg.profile_enable(True)
-    reg.profile_read(reset=True)
-    prof_steps = 2
-    barrier()
-    tp = time.perf_counter()
-    for _ in range(prof_steps):
-        rec_p, _ = step()
-    barrier()
-    profiled_step_ms = (time.perf_counter() - tp) * 1e3 / prof_steps
-    prof = reg.profile_read(reset=True)
-    reg.profile_enable(False)
-    total_pts = sum(n_pts) + len(wl.target)
-    units = {"covariance": prof_steps * total_pts,
-             "linearize": prof_steps * float(np.sum(rec_p["iterations"].astype(np.float64) * np.array(n_pts))),
-             "error": prof_steps * float(np.sum(rec_p["lm_tries"].astype(np.float64) * np.array(n_pts))),
-             "fitness": prof_steps * sum(n_pts)}
-    if method == "NDT_OMP":
-        units["linearize"] = prof_steps * float(np.sum(rec_p["lm_tries"].astype(np.float64) * np.array(n_pts)))
-        units["covariance"] = units["error"] = 0.0
-    roofline = roofline_of(method, prof, units, prof_steps,
-                           "whole-device launches (all candidates of the rank in one launch, HIP events on the engine's stream); the timed region "
-                           "runs the same kernels split over 2 to 4 concurrent lanes (by batch size), whose launches overlap each other",
-                           pmc_ok=(sensor == "HDL-64E" and B == 64 and not a.downsample and not mild and pnh.get("reg_regularization_method") in (None, "PLANE")),
-                           profiled_step_ms=profiled_step_ms, pmc_name="fast_gicp_plane" if pnh.get("reg_regularization_method") == "PLANE" else None)
+    # ---- roofline of the dominant kernel: HIP events on the handle's stream around every launch of each stage (profiled steps of its own: --full)
+    roofline = None
+    if a.full:
+        reg.profile_enable(True)
+        reg.profile_read(reset=True)
+        prof_steps = 2
+        barrier()
+        tp = time.perf_counter()
+        for _ in range(prof_steps):
+            rec_p, _ = step()
+        barrier()
+        profiled_step_ms = (time.perf_counter() - tp) * 1e3 / prof_steps
+        prof = reg.profile_read(reset=True)
+        reg.profile_enable(False)
+        total_pts = sum(n_pts) + len(wl.target)
+        units = {"covariance": prof_steps * total_pts,
+                 "linearize": prof_steps * float(np.sum(rec_p["iterations"].astype(np.float64) * np.array(n_pts))),
+                 "error": prof_steps * float(np.sum(rec_p["lm_tries"].astype(np.float64) * np.array(n_pts))),
+                 "fitness": prof_steps * sum(n_pts)}
+        if method == "NDT_OMP":
+            units["linearize"] = prof_steps * float(np.sum(rec_p["lm_tries"].astype(np.float64) * np.array(n_pts)))
+            units["covariance"] = units["error"] = 0.0
+        roofline = roofline_of(method, prof, units, prof_steps,
+                               "whole-device launches (all candidates of the rank in one launch, HIP events on the engine's stream); the timed region "
+                               "runs the same kernels split over 2 to 4 concurrent lanes (by batch size), whose launches overlap each other",
+                               pmc_ok=(sensor == "HDL-64E" and B == 64 and not a.downsample and not mild and pnh.get("reg_regularization_method") in (None, "PLANE")),
+                               profiled_step_ms=profiled_step_ms, pmc_name="fast_gicp_plane" if pnh.get("reg_regularization_method") == "PLANE" else None)
 
     # ---- the other scene seeds (informational: spread of the metric over scenes)
     by_seed = [round(world * B * steps / dt, 1)]
@@ -801,28 +820,32 @@ def run_single_align(ctx):
         step()
     dt, per_step, r = timed(step, steps)
     dt = max_over_ranks(ctx, dt)
-    step(False)
-    dt_warm, per_warm, _ = timed(step, steps, cold=False)
     err_t, err_r = synth.pose_error(r.matrix(), T)
 
-    reg.profile_enable(True)
-    reg.profile_read(reset=True)
-    prof_steps = 3
-    for _ in range(prof_steps):
-        rp = step()
-    prof = reg.profile_read(reset=True)
-    reg.profile_enable(False)
-    units = {"covariance": prof_steps * (len(tgt) + len(src)), "linearize": prof_steps * float(rp.iterations) * len(src),
-             "error": prof_steps * float(rp.lm_tries) * len(src), "fitness": 0.0}
-    if method == "NDT_OMP":
-        units = {"covariance": 0.0, "linearize": prof_steps * float(rp.lm_tries) * len(src), "error": 0.0, "fitness": 0.0}
-    roofline = roofline_of(method, prof, units, prof_steps, "one registration per launch (HIP events on the engine's stream)", pmc_ok=False)
-    # per-stage roofline (config 5's purpose): algorithmic GB/s of every stage that ran
-    table = stage_table(method)
-    roofline["stages"] = {s: {"kernel": table[s][0], "ms_per_align": round(prof[s][0] / prof_steps, 4), "launches_per_align": prof[s][1] / prof_steps,
-                              "achieved_GBps": round(units[s] * table[s][1] / (prof[s][0] * 1e-3) / 1e9, 1),
-                              "frac_of_8TBps": round(units[s] * table[s][1] / (prof[s][0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
-                          for s in table if prof[s][0] > 0 and units.get(s, 0) > 0}
+    # ---- --full: the warm variant (target cached) and the roofline, each in steps of its own after the timed region
+    dt_warm, per_warm, roofline = None, None, None
+    if a.full:
+        step(False)
+        dt_warm, per_warm, _ = timed(step, steps, cold=False)
+
+        reg.profile_enable(True)
+        reg.profile_read(reset=True)
+        prof_steps = 3
+        for _ in range(prof_steps):
+            rp = step()
+        prof = reg.profile_read(reset=True)
+        reg.profile_enable(False)
+        units = {"covariance": prof_steps * (len(tgt) + len(src)), "linearize": prof_steps * float(rp.iterations) * len(src),
+                 "error": prof_steps * float(rp.lm_tries) * len(src), "fitness": 0.0}
+        if method == "NDT_OMP":
+            units = {"covariance": 0.0, "linearize": prof_steps * float(rp.lm_tries) * len(src), "error": 0.0, "fitness": 0.0}
+        roofline = roofline_of(method, prof, units, prof_steps, "one registration per launch (HIP events on the engine's stream)", pmc_ok=False)
+        # per-stage roofline (config 5's purpose): algorithmic GB/s of every stage that ran
+        table = stage_table(method)
+        roofline["stages"] = {s: {"kernel": table[s][0], "ms_per_align": round(prof[s][0] / prof_steps, 4), "launches_per_align": prof[s][1] / prof_steps,
+                                  "achieved_GBps": round(units[s] * table[s][1] / (prof[s][0] * 1e-3) / 1e9, 1),
+                                  "frac_of_8TBps": round(units[s] * table[s][1] / (prof[s][0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
+                              for s in table if prof[s][0] > 0 and units.get(s, 0) > 0}
 
     by_seed = [round(world * steps / dt, 2)]
     for seed in range(1, ctx["n_seeds"]):
@@ -834,7 +857,7 @@ def run_single_align(ctx):
         by_seed.append(round(world * steps / max_over_ranks(ctx, dts), 2))
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         O, p = oracle_params(reg)
         k = 1 if dense else max(1, min(a.cpu_sample, 3))
 
@@ -855,8 +878,8 @@ def run_single_align(ctx):
                     (f"config 5: dense 1 M-point pair, {method}, max_correspondence_distance 1.0, single cold align" if dense else
                      f"config 2: {sensor} pair (~{len(src)} pts), {method}, single cold align from the identity guess (index + both covariance passes + iterations)"),
                     {"points_per_cloud": int(len(src)), "method": method, "parallelism": f"{world} replicas" if world > 1 else "single GPU"})
-    out.update({"step_ms": percentiles(per_step), "timed_region_s": round(dt, 3), "warm_align_ms": percentiles(per_warm),
-                "warm_value": round(world * steps / dt_warm, 2), "value_by_scene_seed": by_seed,
+    out.update({"step_ms": percentiles(per_step), "timed_region_s": round(dt, 3), "warm_align_ms": percentiles(per_warm) if per_warm else None,
+                "warm_value": round(world * steps / dt_warm, 2) if dt_warm else None, "value_by_scene_seed": by_seed,
                 "value_mean_std_over_seeds": [round(float(np.mean(by_seed)), 2), round(float(np.std(by_seed)), 2)],
                 "iterations": int(r.iterations), "lm_tries": int(r.lm_tries), "converged": int(r.converged),
                 "pose_error_vs_ground_truth": {"translation_m": round(err_t, 5), "rotation_rad": round(err_r, 6)},
@@ -879,7 +902,9 @@ def run_odometry(ctx):
     a = ctx["args"]
     speeds = [a.speed] if a.speed > 0 else [2.0, 8.0]
     kitti_speed = a.speed if a.speed > 0 else 8.0
-    out = odometry_at_speed(ctx, speeds[0], ctx["n_seeds"], not a.no_cpu_baseline)
+    out = odometry_at_speed(ctx, speeds[0], ctx["n_seeds"], a.full and not a.no_cpu_baseline)
+    if not a.full:
+        return out   # a plain run ends with the primary stream's timed region
     keys = ("value", "ms_per_step", "steps", "latency_ms", "mean_iterations", "max_iterations", "keyframes", "us_per_iteration_p50", "trajectory_error_vs_ground_truth",
             "oracle_stream")
     for sp in speeds[1:]:
@@ -924,7 +949,7 @@ def adapter_path_record(ctx, speed):
     sensor = a.sensor or "HDL-64E"
     n = min(a.steps or 60, 60)
     warm = max(1, a.warmup)
-    stream = ctx["workloads"].make_odometry_stream(sensor, 0, warm + n + 1, speed=speed, downsample=a.downsample or None)
+    stream = ctx["workloads"].make_odometry_stream(sensor, 0, warm + n + 1, speed=speed, downsample=a.downsample or None, workers=ctx["cast_workers"])
     rec = {"how": "tests/cpp/adapter_bench.cpp: C++ caller, pcl::Registration base pointer (tests/mock_pcl stand-in of PCL's host-side align()), wall clock around every sweep "
                   "(setInputSource + fresh output cloud + align + getFinalTransformation, and setInputTarget in the sweep that switches the keyframe); keyframe rule: 5 m",
            "method": method, "speed_mps": speed}
@@ -974,7 +999,7 @@ def odometry_at_speed(ctx, speed, n_seeds, with_cpu, pipeline="raw"):
             return d
 
     def run(seed, n_warm, n):
-        stream = ctx["workloads"].make_odometry_stream(sensor, seed, n_warm + n + 1, speed=speed, downsample=a.downsample or None)
+        stream = ctx["workloads"].make_odometry_stream(sensor, seed, n_warm + n + 1, speed=speed, downsample=a.downsample or None, workers=ctx["cast_workers"])
         od = ScanMatchingOdometry(reg, downsample=prefilter, **kf)
         est, its = [], []
         for t, c in zip(stream.stamps[:n_warm + 1], stream.scans[:n_warm + 1]):   # the first call only sets the keyframe
@@ -998,19 +1023,21 @@ def odometry_at_speed(ctx, speed, n_seeds, with_cpu, pipeline="raw"):
     dt = max_over_ranks(ctx, dt)
     n_pts = int(np.mean([len(c) for c in stream.scans]))
 
-    # roofline: a few more sweeps against the current keyframe with the stage timers on
-    reg.profile_enable(True)
-    reg.profile_read(reset=True)
-    prof_sweeps, passes = 4, 0
-    for c in stream.scans[-prof_sweeps:]:
-        reg.setInputSource(prefilter(c) if prefilter else c)
-        rp = reg.align(od.prev_trans)
-        passes += int(rp.lm_tries if method == "NDT_OMP" else rp.iterations)
-    prof = reg.profile_read(reset=True)
-    reg.profile_enable(False)
-    n_reg = int(np.mean(kept)) if kept else n_pts   # points per registered cloud (after the prefilter, if any)
-    units = {"covariance": prof_sweeps * n_reg if method != "NDT_OMP" else 0.0, "linearize": float(passes) * n_reg, "error": 0.0, "fitness": 0.0}
-    roofline = roofline_of(method, prof, units, prof_sweeps, "one registration per launch (HIP events on the engine's stream)", pmc_ok=False)
+    # roofline: a few more sweeps against the current keyframe with the stage timers on (--full)
+    roofline = None
+    if a.full:
+        reg.profile_enable(True)
+        reg.profile_read(reset=True)
+        prof_sweeps, passes = 4, 0
+        for c in stream.scans[-prof_sweeps:]:
+            reg.setInputSource(prefilter(c) if prefilter else c)
+            rp = reg.align(od.prev_trans)
+            passes += int(rp.lm_tries if method == "NDT_OMP" else rp.iterations)
+        prof = reg.profile_read(reset=True)
+        reg.profile_enable(False)
+        n_reg = int(np.mean(kept)) if kept else n_pts   # points per registered cloud (after the prefilter, if any)
+        units = {"covariance": prof_sweeps * n_reg if method != "NDT_OMP" else 0.0, "linearize": float(passes) * n_reg, "error": 0.0, "fitness": 0.0}
+        roofline = roofline_of(method, prof, units, prof_sweeps, "one registration per launch (HIP events on the engine's stream)", pmc_ok=False)
 
     by_seed = [round(world * steps / dt, 2)]
     n_extra = max(10, steps // 3)
@@ -1020,7 +1047,7 @@ def odometry_at_speed(ctx, speed, n_seeds, with_cpu, pipeline="raw"):
 
     # ---- the CPU oracle through the same caller on the head of the same stream: rate (cpu_baseline) and agreement of the trajectories
     cpu, oracle_stream = None, None
-    if rank == 0 and world == 1 and (with_cpu or a.oracle_sweeps > 0):
+    if rank == 0 and world == 1 and a.full and (with_cpu or a.oracle_sweeps > 0):
         O, p = oracle_params(reg)
         k = max(2, min(a.cpu_sample, 4))
         oracle_pf = None

@@ -1,7 +1,8 @@
 """bench.py's output contract, checked without a GPU: the script is run as the driver runs it (`python bench.py --gpus 1
 --steps K --warmup W`, and through torch.distributed.run with two ranks) against the host emulation of the kernels
 (HGS_BENCH_EMULATED_LIB, tests/emul/simt.py) on a tiny workload.  Only the shape of the JSON line is asserted — the numbers
-of an emulated run mean nothing, and the line says so in `data`."""
+of an emulated run mean nothing, and the line says so in `data`.  The tests of the roofline, the CPU baselines and the sub-records
+run the script with --full; a plain run ends with its timed steps (test_plain_run_ends_with_the_timed_steps)."""
 import json
 import os
 import subprocess
@@ -49,7 +50,7 @@ SMALL = ["--candidates", "2", "--distinct", "2", "--sensor", "VLP-16", "--downsa
 
 
 def test_single_rank_line():
-    rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *SMALL, "--cpu-sample", "1", "--ndt-steps", "2"])
+    rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", *SMALL, "--cpu-sample", "1", "--ndt-steps", "2"])
     _check(rec, 1, 2, 1, 2)
     cpu = rec["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["unit"] == "registrations/sec" and cpu["value"] > 0 and cpu["cores"] >= 1 and cpu["sample"]
@@ -88,7 +89,7 @@ def test_two_ranks_through_torch_distributed_run(tmp_path):
     port = s.getsockname()[1]
     s.close()
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", *SMALL, "--method", "NDT_OMP", "--ndt-line-search", "--strong-candidates", "4",
+                os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", *SMALL, "--method", "NDT_OMP", "--ndt-line-search", "--strong-candidates", "4",
                 "--dump-outputs", str(tmp_path)])
     _check(rec, 2, 2, 1, 2)
     out = _load_dump(tmp_path)
@@ -105,7 +106,7 @@ def test_two_ranks_through_torch_distributed_run(tmp_path):
 def test_other_baseline_configs_emit_the_same_contract(config, extra):
     """--config 2 / 3 / 4 (5 is config 2's code path on a 1 M-point pair): one JSON line each with roofline, cpu_baseline and the
     per-step percentiles."""
-    rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", str(config), *extra, "--cpu-sample", "2"])
+    rec = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--config", str(config), *extra, "--cpu-sample", "2"])
     for key, typ in REQUIRED.items():
         assert key in rec, key
     assert rec["unit"] == "registrations/sec" and rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["value"] > 0
@@ -141,7 +142,7 @@ def test_eight_ranks_fall_back_to_the_torch_exchange_when_the_trial_step_fails()
     """The driver's --gpus 8 launch, emulated: the untimed trial step of the library's RCCL exchange fails on ONE rank (injected) -> the MIN all-reduce makes
     every rank exchange through torch.distributed; the line says so, carries every rank's step time and the config-4 strong-scaling sub-record."""
     rec = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-                os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--candidates", "1", "--distinct", "1", "--sensor", "VLP-16", "--downsample", "0.6",
+                os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--full", "--candidates", "1", "--distinct", "1", "--sensor", "VLP-16", "--downsample", "0.6",
                 "--strong-candidates", "8"], extra_env={"HGS_BENCH_TEST_EXCHANGE_FAILS": "5", "OMP_NUM_THREADS": "1"})
     _check(rec, 8, 1, 1, 1)
     assert "fallback" in rec["config"]["exchange"] and "torch.distributed" in rec["config"]["exchange"]
@@ -164,6 +165,33 @@ def test_single_process_mode_drives_one_engine_per_gpu_from_threads():
 def _load_dump(d):
     import numpy as np
     return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus")
+FULL_ONLY = {0: ("roofline", "cpu_baseline", "resident_keyframes_value", "fast_gicp_plane", "ndt_omp", "r02_candidate_set"),
+             2: ("roofline", "cpu_baseline", "warm_value", "warm_align_ms"),
+             3: ("roofline", "cpu_baseline", "oracle_stream", "at_8_mps", "adapter_path", "kitti_prefilter_ndt_omp", "kitti_launch_fast_gicp")}
+
+
+@pytest.mark.parametrize("config,extra", [(0, SMALL), (2, ["--sensor", "VLP-16", "--downsample", "0.5"]), (3, ["--sensor", "VLP-16", "--downsample", "0.5"])])
+def test_plain_run_ends_with_the_timed_steps(config, extra, tmp_path):
+    """Without --full the line carries the headline figure of the same timed steps and nothing that takes a run of its own: no roofline, CPU baseline,
+    resident / warm variant, other scene seed or sub-record.  --full adds them after the timed region: the headline fields other than the measured time
+    and the --dump-outputs arrays of the two runs are the same."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", str(config), *extra, "--cpu-sample", "1", "--ndt-steps", "2"]
+    plain = _run([*cmd, "--dump-outputs", str(tmp_path / "plain")])
+    full = _run([*cmd, "--full", "--dump-outputs", str(tmp_path / "full")])
+    assert plain["full"] is False and full["full"] is True
+    for key in HEADLINE:
+        assert plain[key] == full[key] or key == "value", key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["config"] == full["config"] and len(plain["value_by_scene_seed"]) == 1
+    for key in FULL_ONLY[config]:
+        assert plain.get(key) is None and full[key] is not None, key
+    a, b = _load_dump(tmp_path / "plain"), _load_dump(tmp_path / "full")
+    assert set(a) == set(b) and "final_transformation" in a
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
 
 
 @pytest.mark.parametrize("config,extra", [(0, [*SMALL, "--no-ndt-record", "--no-plane-record"]), (2, ["--sensor", "VLP-16", "--downsample", "0.5"]),
