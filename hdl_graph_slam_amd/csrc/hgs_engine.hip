@@ -2773,6 +2773,43 @@ int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17
   return status_of_current_exception(h);
 }
 
+int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_in[12], double mse_prev, int32_t iterations_in, double T12_out[12],
+                       int32_t flags3[3], double* mse) try {
+  std::unique_lock<std::recursive_mutex> api_lock__;
+  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  if (!h || !sums17 || !T12_in || !T12_out || !flags3 || !mse) return HGS_ERR_INVALID_ARGUMENT;
+  if (h->prm.method != HGS_ICP) return HGS_ERR_UNSUPPORTED;
+  if (!h->source) return HGS_ERR_NO_SOURCE;  // (k_icp_solve takes its tile count from the source's nvalid)
+  HGS_TRY(set_device(h));
+  hgs_cloud* s = h->source;
+  std::vector<hgs_cloud*> src{s};
+  HGS_TRY(ensure_index(h, src));
+  const int max_blocks = std::max(1, ((int)s->n_input + kTileNN - 1) / kTileNN);
+  const CloudDesc* d_descs = nullptr;
+  HGS_TRY(upload_descs(h, src, false, &d_descs, nullptr));
+  IcpState st;
+  for (int i = 0; i < 12; i++) st.x.m[i] = T12_in[i];
+  st.mse = DBL_MAX, st.mse_prev = mse_prev, st.phase = ICP_RUN, st.iterations = iterations_in, st.passes = 0, st.converged = 0;
+  Progress prog;
+  HGS_TRY(make_progress(h, 0, 1, &prog));
+  HGS_HIP(h, h->states.reserve(sizeof(IcpState)));
+  HGS_HIP(h, h->partials.reserve((size_t)max_blocks * kAccIcp * sizeof(double)));
+  HGS_HIP(h, hipMemsetAsync(prog.dev, 0, 2 * sizeof(int), h->stream));
+  HGS_HIP(h, hipMemcpyAsync(h->states.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+  HGS_HIP(h, hipMemsetAsync(h->partials.p, 0, (size_t)max_blocks * kAccIcp * sizeof(double), h->stream));  // every tile row but row 0
+  HGS_HIP(h, hipMemcpyAsync(h->partials.p, sums17, kAccIcp * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  launch_icp_solve(h->stream, d_descs, h->states.as<IcpState>(), icp_consts(h->prm), h->partials.as<double>(), max_blocks, 1, prog);
+  HGS_HIP(h, hipGetLastError());
+  HGS_HIP(h, hipMemcpyAsync(&st, h->states.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < 12; i++) T12_out[i] = st.x.m[i];
+  flags3[0] = st.converged, flags3[1] = st.phase == ICP_DONE ? 1 : 0, flags3[2] = st.iterations;
+  *mse = st.mse;
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells) try {
   std::unique_lock<std::recursive_mutex> api_lock__;
   if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);

@@ -284,6 +284,19 @@ class RegistrationHIP:
         self._check(L.lib().hgs_debug_icp_correspond(self._h, T12.ctypes.data_as(vp), sums.ctypes.data_as(vp), corr.ctypes.data_as(vp)))
         return sums, corr
 
+    def icp_step(self, sums17, T_in=None, mse_prev: float = L.DBL_MAX, iterations_in: int = 0):
+        """One ICP control step (k_icp_solve) on the 17 sums of a correspondence pass, from the state (T_in, mse_prev, iterations_in):
+        (T_out 4x4 in double, converged, done, iterations, mse).  Needs a source, no target."""
+        T12 = np.ascontiguousarray((np.eye(4) if T_in is None else np.asarray(T_in, np.float64))[:3, :4])
+        sums = np.ascontiguousarray(sums17, np.float64).reshape(17)
+        out, flags, mse = np.zeros((3, 4)), np.zeros(3, np.int32), np.zeros(1)
+        vp = C.c_void_p
+        self._check(L.lib().hgs_debug_icp_step(self._h, sums.ctypes.data_as(vp), T12.ctypes.data_as(vp), float(mse_prev), int(iterations_in),
+                                               out.ctypes.data_as(vp), flags.ctypes.data_as(vp), mse.ctypes.data_as(vp)))
+        T = np.eye(4)
+        T[:3] = out
+        return T, int(flags[0]), int(flags[1]), int(flags[2]), float(mse[0])
+
     def ndt_cells(self, cap: int = 1 << 20):
         ijk, mean, icov, npts = np.zeros((cap, 3), np.int32), np.zeros((cap, 3)), np.zeros((cap, 6), np.float32), np.zeros(cap, np.int32)
         n = C.c_int32()

@@ -289,6 +289,12 @@ int hgs_debug_gicp_linearize(hgs_handle* h, const double T12[12], double* H36, d
  * icp_reciprocal: sums17 = [pairs, sum p (3), sum q (3), sum q p^T (9, row-major), sum d2] over the kept pairs (p the moved source
  * point as searched, q its target point), and per source point (original order) the original target index of its pair or -1. */
 int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17, int32_t* corr);
+/* ICP: one control step (the product kernel k_icp_solve: Umeyama step from the sums, final = Delta * final, DefaultConvergenceCriteria)
+ * on caller-made sums of one correspondence pass, with the engine's parameters: the state is (T12_in, mse_prev, iterations_in), sums17 as
+ * above.  T12_out (double, row-major 3x4 — not the float of hgs_result), flags3 = {converged, done, iterations}, *mse = the state's mse
+ * (DBL_MAX when no step was taken).  Needs a source (the kernel takes its tile count from it: HGS_ERR_NO_SOURCE), no target. */
+int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_in[12], double mse_prev, int32_t iterations_in,
+                       double T12_out[12], int32_t flags3[3] /* converged, done, iterations */, double* mse);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
 /* One NDT derivative pass at p = (tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */

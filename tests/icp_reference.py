@@ -151,30 +151,38 @@ class IcpReference:
         p64, q64 = p.astype(np.float64), q.astype(np.float64)
         return np.concatenate([[len(p)], p64.sum(0), q64.sum(0), (q64.T @ p64).reshape(9), [d2.astype(np.float64).sum()]])
 
+    def after_pass(self, sums, T, mse_prev, iterations, delta=None, mse=None) -> dict:
+        """What follows a correspondence pass (hgs_icp.h icp_after_pass) from the pass's 17 sums and the state (T, mse_prev, iterations):
+        fewer than 3 pairs -> not converged, done, state kept; else the Umeyama step (delta, or the step from the sums), T = Delta T,
+        ++iterations and DefaultConvergenceCriteria's tests in their order.  align() hands in the step and the mse it has from the pairs themselves."""
+        sums = np.asarray(sums, np.float64)
+        T = np.asarray(T, np.float64)
+        if not sums[0] >= 3:
+            return {"T": T, "converged": False, "done": True, "iterations": iterations, "mse": None, "mse_prev": mse_prev}
+        D = umeyama_from_sums(sums) if delta is None else delta
+        iterations += 1
+        mse = float(sums[16] / sums[0]) if mse is None else mse
+        converged = iterations >= self.max_iterations
+        if not converged:
+            cos_angle = 0.5 * (np.trace(D[:3, :3]) - 1.0)
+            converged = bool(cos_angle >= self.rot_thr and float(D[:3, 3] @ D[:3, 3]) <= self.eps)
+        if not converged:
+            converged = abs(mse - mse_prev) < 1e-12
+        return {"T": D @ T, "converged": converged, "done": converged, "iterations": iterations, "mse": mse, "mse_prev": mse_prev if converged else mse}
+
     def align(self, guess=None) -> dict:
         T = np.eye(4) if guess is None else np.asarray(guess, np.float32).astype(np.float64)   # the device receives the guess as float
         mse_prev, mse = DBL_MAX, DBL_MAX
         iterations = passes = 0
-        converged = False
         while True:
             _, _, p, q, d2 = self.correspond(T)
             passes += 1
-            if len(p) < 3:
-                converged = False
-                break
-            D = umeyama(p, q)
-            T = D @ T
-            iterations += 1
-            mse = float(d2.astype(np.float64).mean())
-            if iterations >= self.max_iterations:
-                converged = True
-                break
-            cos_angle = 0.5 * (np.trace(D[:3, :3]) - 1.0)
-            if cos_angle >= self.rot_thr and float(D[:3, 3] @ D[:3, 3]) <= self.eps:
-                converged = True
-                break
-            if abs(mse - mse_prev) < 1e-12:
-                converged = True
-                break
-            mse_prev = mse
-        return {"T": T, "converged": converged, "iterations": iterations, "passes": passes, "mse": mse}
+            s = np.zeros(17)
+            s[0] = len(p)
+            some = len(p) >= 3
+            o = self.after_pass(s, T, mse_prev, iterations, delta=umeyama(p, q) if some else None, mse=float(d2.astype(np.float64).mean()) if some else None)
+            T, iterations, mse_prev = o["T"], o["iterations"], o["mse_prev"]
+            if some:
+                mse = o["mse"]
+            if o["done"]:
+                return {"T": T, "converged": o["converged"], "iterations": iterations, "passes": passes, "mse": mse}

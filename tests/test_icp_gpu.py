@@ -1,6 +1,8 @@
 """ICP_HIP (HGS_ICP) on the MI355X against the restatement of tests/icp_reference.py: the vlp16 / hdl32 / hdl32_raw pairs of
 tests/test_hip_parity.py with reciprocal correspondences off and on, the stage hook, a 64-candidate loop-closure batch against the
-sequential reference with the same selection, and the pcl::Registration adapter through tests/cpp/icp_adapter_main.cpp."""
+sequential reference with the same selection, the pcl::Registration adapter through tests/cpp/icp_adapter_main.cpp, and the shared checks of
+tests/icp_checks.py on the solve step (hgs_debug_icp_step), the exact threshold rule, awkward sources, degenerate scenes and the fitness behind an
+align — the same ones tests/test_icp_simt_host.py runs on the host emulation."""
 import os
 import subprocess
 
@@ -118,3 +120,67 @@ def test_icp_adapter_matches_python_mirror(tmp_path, reciprocal):
     Tc = np.array([float(v) for v in out[3].split()], np.float32).reshape(4, 4).T
     assert np.array_equal(Tc, r.matrix())
     reg.close()
+
+
+# ---- the solve step through hgs_debug_icp_step, the threshold rule, small / awkward sources, degenerate geometry, fitness behind an align
+def _make(p, src=None, tgt=None):
+    e = _engine(p)
+    if tgt is not None:
+        e.setInputTarget(tgt)
+    if src is not None:
+        e.setInputSource(src)
+    return e
+
+
+def test_icp_step_hook_needs_a_source_and_the_icp_method():
+    IC.check_step_hook_errors(_make)
+
+
+@pytest.fixture(scope="module")
+def step_engine():
+    e = _make(IC.icp_params(), IC.hook_source())
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("case", IC.UMEYAMA_CASES)
+def test_icp_umeyama_step_on_synthesised_sums(step_engine, case):
+    IC.check_umeyama_step(step_engine, case)
+
+
+def test_icp_after_pass_decision_table():
+    IC.check_decision_table(lambda p: _make(p, IC.hook_source()))
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_threshold_rule_is_exact(reciprocal):
+    IC.check_threshold_rule(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_small_sources(reciprocal):
+    IC.check_small_sources(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_non_finite_source_rows(reciprocal):
+    IC.check_non_finite_rows(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_empty_source(reciprocal):
+    IC.check_empty_source(_make, reciprocal)
+
+
+def test_icp_duplicated_points_under_the_reciprocal_test():
+    IC.check_duplicated_points(_make)
+
+
+def test_icp_degenerate_geometry():
+    IC.check_degenerate_geometry(_make)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_fitness_behind_an_align_equals_the_oracle(reciprocal):
+    tgt, src, T = synth.make_pair("VLP-16", 1, downsample=0.45)
+    IC.check_fitness_after_align(_make, tgt, src, T @ synth.pose_matrix([0.3, -0.2, 0.05], [0.01, -0.005, 0.03]), reciprocal)

@@ -1,7 +1,9 @@
 """ICP_HIP (HGS_ICP) on the CPU: the product kernels k_icp_correspond / k_icp_solve and the engine's ICP branch, compiled for the host against
 the SIMT emulation of tests/emul and driven through the C-ABI and the Python mirror, against the restatement of tests/icp_reference.py on
 pairs of at most ~6.5 k points: the align with reciprocal correspondences off and on, identity and non-identity guesses; the stage hook;
-the < 3 correspondences and max_iterations exits; a 6-candidate loop-closure batch against six single aligns."""
+the < 3 correspondences and max_iterations exits; a 6-candidate loop-closure batch against six single aligns; and the shared checks of
+tests/icp_checks.py on the solve step (hgs_debug_icp_step: every branch of svd3, the decision table of icp_after_pass), the exact
+max_correspondence_distance rule, small / non-finite / empty / duplicated sources, degenerate scenes and the fitness behind an align."""
 import numpy as np
 import pytest
 
@@ -108,3 +110,67 @@ def test_icp_loop_match_batch_equals_single_aligns(reciprocal):
     for c in cands:
         c.close()
     e.close()
+
+
+# ---- the solve step through hgs_debug_icp_step, the threshold rule, small / awkward sources, degenerate geometry, fitness behind an align
+def _make(p, src=None, tgt=None):
+    e = _engine(p)
+    if tgt is not None:
+        e.setInputTarget(tgt)
+    if src is not None:
+        e.setInputSource(src)
+    return e
+
+
+def test_icp_step_hook_needs_a_source_and_the_icp_method():
+    IC.check_step_hook_errors(_make)
+
+
+@pytest.fixture(scope="module")
+def step_engine():
+    e = _make(IC.icp_params(), IC.hook_source())
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("case", IC.UMEYAMA_CASES)
+def test_icp_umeyama_step_on_synthesised_sums(step_engine, case):
+    IC.check_umeyama_step(step_engine, case)
+
+
+def test_icp_after_pass_decision_table():
+    IC.check_decision_table(lambda p: _make(p, IC.hook_source()))
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_threshold_rule_is_exact(reciprocal):
+    IC.check_threshold_rule(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_small_sources(reciprocal):
+    IC.check_small_sources(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_non_finite_source_rows(reciprocal):
+    IC.check_non_finite_rows(_make, reciprocal)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_empty_source(reciprocal):
+    IC.check_empty_source(_make, reciprocal)
+
+
+def test_icp_duplicated_points_under_the_reciprocal_test():
+    IC.check_duplicated_points(_make)
+
+
+def test_icp_degenerate_geometry():
+    IC.check_degenerate_geometry(_make)
+
+
+@pytest.mark.parametrize("reciprocal", [False, True])
+def test_icp_fitness_behind_an_align_equals_the_oracle(reciprocal):
+    tgt, src, T = _pair("vlp16")
+    IC.check_fitness_after_align(_make, tgt, src, T @ synth.pose_matrix([0.3, -0.2, 0.05], [0.01, -0.005, 0.03]), reciprocal)
