@@ -3,6 +3,7 @@
 //   f1  InformationMatrixCalculator::calc_fitness_score   src/hdl_graph_slam/information_matrix_calculator.cpp:49-80   -> hgs_calc_fitness_score
 //   f2  PrefilteringNodelet::cloud_callback :131-133      apps/prefiltering_nodelet.cpp (distance filter, downsample, outlier removal) -> hgs_prefilter
 //   f3  MapCloudGenerator::generate                       src/hdl_graph_slam/map_cloud_generator.cpp:13-51              -> hgs_map_cloud_generate
+//   12  FloorDetectionNodelet::detect                     apps/floor_detection_nodelet.cpp:110-180 (through adapters/floor_detection_hip.hpp) -> hgs_detect_floor
 //
 // integration/hdl_graph_slam_hip.patch calls them from the reference's own functions behind #ifdef USE_HGS_HIP; every call returns false when the
 // device path could not run (no engine, out of memory, an argument the device refuses) and the reference's CPU code below the hunk runs instead —
@@ -125,7 +126,52 @@ public:
       out.points.resize(hgs_cloud_size(filtered));
       ok = out.points.empty() || check(hgs_cloud_download(filtered, out.points.data(), sizeof(PointT)), "hgs_cloud_download");
     }
+    if (ok && keep_prefiltered_) {  // (floor detection, below: the same sweep comes back as /filtered_points)
+      if (prefiltered_) hgs_cloud_destroy(prefiltered_);
+      prefiltered_ = filtered, filtered = nullptr;
+      if (!out.points.empty()) {
+        const PointT &a = out.points.front(), &b = out.points.back();
+        const float e[6] = {a.x, a.y, a.z, b.x, b.y, b.z};
+        std::memcpy(prefiltered_ends_, e, sizeof(e));
+      } else {
+        hgs_cloud_destroy(prefiltered_), prefiltered_ = nullptr;
+      }
+    }
     if (filtered) hgs_cloud_destroy(filtered);
+    device_calls_ += ok ? 1 : 0;
+    return ok;
+  }
+
+  // row 12 — FloorDetectionNodelet::detect (apps/floor_detection_nodelet.cpp:110-180) on the device: adapters/floor_detection_hip.hpp calls this.  The
+  // nodelet's input is the prefilter's output (:44): with keepPrefiltered(true) the last prefilter() result stays resident, and a cloud of the same size
+  // whose first and last points carry the same bits is taken from the device instead of being uploaded again.  `filtered` / `inliers` (null ok): the clouds
+  // of floor_filtered_pub / floor_points_pub (:127-130, :168-177).
+  void keepPrefiltered(bool on) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    keep_prefiltered_ = on;
+    if (!on && prefiltered_) hgs_cloud_destroy(prefiltered_), prefiltered_ = nullptr;
+  }
+  size_t resident_hits() const { return resident_hits_; }  // floor detections that found their input resident
+  bool detect_floor(const Cloud& cloud, const hgs_floor_params& params, hgs_floor_result* result, Cloud* filtered, Cloud* inliers) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    if (!enabled_ || !result || cloud.points.empty()) return false;
+    if (!engine()) return false;
+    hgs_cloud* in = nullptr;
+    bool uploaded = false;
+    if (prefiltered_ && hgs_cloud_size(prefiltered_) == cloud.points.size() && same_ends(cloud)) {
+      in = prefiltered_;
+      resident_hits_++;
+    } else {
+      if (!check(hgs_cloud_create(handle_, cloud.points.data(), cloud.points.size(), sizeof(PointT), &in), "hgs_cloud_create")) return false;
+      uploaded = true;
+    }
+    hgs_cloud *f = nullptr, *i = nullptr;
+    bool ok = check(hgs_detect_floor(handle_, in, &params, result, filtered ? &f : nullptr, inliers ? &i : nullptr), "hgs_detect_floor");
+    if (ok && filtered) ok = fetch(f, *filtered);
+    if (ok && inliers) ok = fetch(i, *inliers);
+    if (f) hgs_cloud_destroy(f);
+    if (i) hgs_cloud_destroy(i);
+    if (uploaded) hgs_cloud_destroy(in);
     device_calls_ += ok ? 1 : 0;
     return ok;
   }
@@ -167,6 +213,21 @@ private:
   size_t bytes_ = 0, max_bytes_ = (size_t)8 << 30, device_calls_ = 0;
   uint64_t tick_ = 0;
   std::string last_error_;
+  bool keep_prefiltered_ = false;
+  hgs_cloud* prefiltered_ = nullptr;  // the last prefilter() output (keepPrefiltered)
+  size_t resident_hits_ = 0;
+  float prefiltered_ends_[6] = {0, 0, 0, 0, 0, 0};
+
+  bool same_ends(const Cloud& c) const {
+    const PointT &a = c.points.front(), &b = c.points.back();
+    const float e[6] = {a.x, a.y, a.z, b.x, b.y, b.z};
+    return std::memcmp(e, prefiltered_ends_, sizeof(e)) == 0;
+  }
+  bool fetch(hgs_cloud* dev, Cloud& out) {  // a resident cloud (null: none) as PointXYZI records
+    out.points.resize(dev ? hgs_cloud_size(dev) : 0);
+    out.width = (unsigned)out.points.size(), out.height = 1;
+    return out.points.empty() || check(hgs_cloud_download(dev, out.points.data(), sizeof(PointT)), "hgs_cloud_download");
+  }
 
   bool engine() {
     if (handle_) return true;
@@ -217,6 +278,7 @@ private:
     return rc == HGS_OK;
   }
   void release_locked() {
+    if (prefiltered_) hgs_cloud_destroy(prefiltered_), prefiltered_ = nullptr;
     while (!clouds_.empty()) drop(clouds_.begin());
     if (handle_) hgs_destroy(handle_);
     handle_ = nullptr, create_failed_ = false;

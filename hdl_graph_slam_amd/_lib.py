@@ -59,6 +59,26 @@ class HgsPrefilterParams(C.Structure):
     ]
 
 
+class HgsFloorParams(C.Structure):
+    """hgs_floor_params: the rosparams of apps/floor_detection_nodelet.cpp:57-63 and the constants of :140 / :219."""
+    _fields_ = [
+        ("tilt_deg", C.c_double), ("sensor_height", C.c_double), ("height_clip_range", C.c_double),
+        ("floor_pts_thresh", C.c_int32), ("use_normal_filtering", C.c_int32),
+        ("floor_normal_thresh", C.c_double), ("normal_filter_thresh", C.c_double),
+        ("normal_k", C.c_int32), ("ransac_max_iterations", C.c_int32),
+        ("ransac_distance_threshold", C.c_double), ("ransac_probability", C.c_double),
+        ("seed", C.c_uint32), ("reserved", C.c_int32),
+    ]
+
+
+class HgsFloorResult(C.Structure):
+    _fields_ = [
+        ("coeffs", C.c_float * 4), ("detected", C.c_int32), ("reason", C.c_int32),
+        ("n_clipped", C.c_uint32), ("n_filtered", C.c_uint32), ("n_inliers", C.c_uint32), ("ransac_iterations", C.c_int32),
+    ]
+
+
+HGS_FLOOR_DETECTED, HGS_FLOOR_TOO_FEW_POINTS, HGS_FLOOR_TOO_FEW_INLIERS, HGS_FLOOR_NOT_VERTICAL = 0, 1, 2, 3
 HGS_DOWNSAMPLE_NONE, HGS_DOWNSAMPLE_VOXELGRID, HGS_DOWNSAMPLE_APPROX_VOXELGRID = 0, 1, 2
 HGS_OUTLIER_NONE, HGS_OUTLIER_STATISTICAL, HGS_OUTLIER_RADIUS = 0, 1, 2
 
@@ -87,6 +107,7 @@ EXPORTS = [
     "hgs_loop_match_batch", "hgs_select_best", "hgs_calc_fitness_score",
     "hgs_comm_get_unique_id", "hgs_comm_init", "hgs_comm_finalize", "hgs_loop_match_batch_sharded",
     "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_cloud_download", "hgs_map_cloud_generate",
+    "hgs_floor_params_default", "hgs_detect_floor", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
     "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
 ]
@@ -135,6 +156,10 @@ def lib():
     L.hgs_prefilter_deskewed.argtypes = [vp, vp, sz, sz, C.POINTER(HgsPrefilterParams), vp, C.c_double, C.POINTER(vp)]
     L.hgs_cloud_download.argtypes = [vp, vp, sz]
     L.hgs_map_cloud_generate.argtypes = [vp, C.POINTER(vp), vp, sz, C.c_double, C.POINTER(vp)]
+    L.hgs_floor_params_default.argtypes = [C.POINTER(HgsFloorParams)]
+    L.hgs_detect_floor.argtypes = [vp, vp, C.POINTER(HgsFloorParams), C.POINTER(HgsFloorResult), C.POINTER(vp), C.POINTER(vp)]
+    L.hgs_debug_floor_filter.argtypes = [vp, vp, C.POINTER(HgsFloorParams), vp, vp, vp]
+    L.hgs_debug_floor_ransac_counts.argtypes = [vp, vp, C.POINTER(HgsFloorParams), C.c_uint32, C.c_uint32, vp, vp]
     L.hgs_profile_enable.argtypes = [vp, C.c_int]
     L.hgs_profile_read.argtypes = [vp, vp, vp, C.c_int]
     L.hgs_synchronize.argtypes = [vp]

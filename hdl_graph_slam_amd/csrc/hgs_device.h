@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hgs_gicp.h"
+#include "hgs_floor.h"
 #include "hgs_icp.h"
 #include "hgs_ndt.h"
 #include "hgs_vgicp.h"
@@ -224,6 +225,18 @@ void launch_pf_radius_flags(hipStream_t s, CloudDesc d, float r2, int min_neighb
 void launch_pf_mean_knn_dist(hipStream_t s, CloudDesc d, int mean_k, double* dist);
 void launch_pf_statistical(hipStream_t s, const double* dist, int n, double* stats, double stddev_mul, unsigned* keep);
 void launch_pf_to_cloud(hipStream_t s, const float4* in, int n, float4* raw, float* intensity, CloudMeta* meta_to_reset, const CloudDesc* desc = nullptr, CloudDesc* desc_out = nullptr);
+
+// floor detection (apps/floor_detection_nodelet.cpp:110-238; hgs_floor.h)
+void launch_floor_clip_flags(hipStream_t s, const float4* raw, const float* intensity, int n, FloorConsts c, float4* out /* {x, y, z, intensity} */, unsigned* keep);
+void launch_knn_cov_raw(hipStream_t s, const CloudDesc* descs /* one cloud */, int max_n, int k, int qpw, int gather, double* raw_stage /* max_n * 6 doubles, sorted order */);
+void launch_floor_normal_flags(hipStream_t s, CloudDesc d, const double* raw_cov, FloorConsts c, unsigned* keep /* original order */, double* normals /* [n][3] or null */);
+void launch_floor_ransac_init(hipStream_t s, FloorRansacState* st, int max_iterations, Progress prog);
+void launch_floor_ransac_planes(hipStream_t s, const float4* pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st /* null: always */, double* planes /* [nh][4] */,
+                                int* counts /* [nh], zeroed here */);
+void launch_floor_ransac_count(hipStream_t s, const float4* pts, int n, double thresh, const double* planes, int nh, const FloorRansacState* st /* null: always */, int* counts);
+void launch_floor_ransac_decide(hipStream_t s, const int* counts, const double* planes, int i0, int nh, int n, int max_iterations, double log_prob, FloorRansacState* st,
+                                Progress prog);
+void launch_floor_inlier_flags(hipStream_t s, const float4* pts, int n, const FloorRansacState* st, double thresh, unsigned* keep);
 
 // stage-level test hooks
 void launch_gicp_debug_state(hipStream_t s, GicpState* st, const double* T12_dev);

@@ -320,6 +320,7 @@ struct hgs_handle {
   // launches fill the device on their own and two chains are enough to cover each other's solves and tails.
   int prefilter_fast = 1;  // hgs_prefilter: distance filter inside the voxel grid's kernels, RadiusOutlierRemoval on the voxel grid (0: the separate passes + search tree; A/B, tests)
   int upload_trace = 0;
+  int floor_chunk = 64;    // hgs_detect_floor: hypotheses per RANSAC round (planes + count + decide); the result does not depend on it (tests)
   int early_run_ahead = 2;  // rounds the host keeps queued in front of a single registration that hands its result over early (the surplus drains behind the caller's back; 3 / 4 measured: no gain for the odometry source, config 2 0.837 -> 0.844 / 0.852 ms back to back: profiles/r06_ab16_early_run_ahead.log)
   int early_result = 1;    // a single registration in two-launch rounds hands its result over in host-mapped memory (run_batch; 0: result kernel + copy + synchronisation)
   PinnedBuffer h_early;                // the host-mapped record
@@ -961,6 +962,7 @@ int hw_queue_budget() {
   }();
   return budget;
 }
+constexpr int kFloorMaxChunk = 4096;  // hypotheses per RANSAC round of hgs_detect_floor ("floor_chunk")
 constexpr int kMaxLanes = 8;  // HGS_BATCH_LANES up to 8 (A/B runs); the default choice stays at 3-4 and is further bounded by the queue budget above
 
 // Progress mirror of one lane of a batch: device counters + two ints of host-mapped pinned memory the kernels write into.
@@ -1471,6 +1473,7 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
   else if (k == "nn_qpw32_below") h->nn_qpw32_below = std::max(0, value);
   else if (k == "upload_trace") h->upload_trace = value != 0 ? 1 : 0;
   else if (k == "prefilter_fast") h->prefilter_fast = value != 0 ? 1 : 0;
+  else if (k == "floor_chunk") h->floor_chunk = std::max(1, std::min(kFloorMaxChunk, value));
   else {
     h->err = "hgs_debug_set_option: unknown option '" + k + "'";
     return HGS_ERR_INVALID_ARGUMENT;
@@ -2575,6 +2578,288 @@ extern "C" int hgs_map_cloud_generate(hgs_handle* h, hgs_cloud* const* keyframes
   }
   HGS_HIP(h, hipGetLastError());
   return cloud_from_device(h, result, m, out);
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+// ---- floor detection (apps/floor_detection_nodelet.cpp:110-238) ----------------------------------------------
+extern "C" int hgs_floor_params_default(hgs_floor_params* p) try {
+  if (!p) return HGS_ERR_INVALID_ARGUMENT;
+  std::memset(p, 0, sizeof(*p));
+  p->tilt_deg = 0.0;               // floor_detection_nodelet.cpp:57
+  p->sensor_height = 2.0;          // :58
+  p->height_clip_range = 1.0;      // :59
+  p->floor_pts_thresh = 512;       // :60
+  p->floor_normal_thresh = 10.0;   // :61
+  p->use_normal_filtering = 1;     // :62
+  p->normal_filter_thresh = 20.0;  // :63
+  p->normal_k = 10;                // :219
+  p->ransac_max_iterations = 1000;     // pcl::SampleConsensus
+  p->ransac_distance_threshold = 0.1;  // :140
+  p->ransac_probability = 0.99;        // pcl::SampleConsensus
+  p->seed = 0;
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(nullptr);
+}
+
+namespace {
+
+bool floor_params_valid(const hgs_floor_params* p) {
+  return std::isfinite(p->tilt_deg) && std::isfinite(p->sensor_height) && std::isfinite(p->height_clip_range) && p->height_clip_range >= 0 && p->floor_pts_thresh >= 0 &&
+         std::isfinite(p->floor_normal_thresh) && p->floor_normal_thresh >= 0 && std::isfinite(p->normal_filter_thresh) && p->normal_filter_thresh >= 0 &&
+         p->normal_k >= 3 && p->normal_k <= 64 && p->ransac_max_iterations >= 0 && std::isfinite(p->ransac_distance_threshold) && p->ransac_distance_threshold >= 0 &&
+         p->ransac_probability > 0 && p->ransac_probability < 1;
+}
+
+FloorConsts floor_consts(const hgs_floor_params* p) {
+  FloorConsts c{};
+  // tilt_matrix (:112-113): the angle is a float (Eigen::AngleAxisf); z' = (R p).z = -sin * x + cos * z, r = R^-1 e_z = (-sin, 0, cos)
+  const double angle = (double)(float)(p->tilt_deg * M_PI / 180.0);
+  c.rx = p->tilt_deg == 0.0 ? 0.f : -(float)std::sin(angle);
+  c.rz = p->tilt_deg == 0.0 ? 1.f : (float)std::cos(angle);
+  c.nrx = (double)c.rx, c.nrz = (double)c.rz;
+  c.clip_lo = (float)(p->sensor_height + p->height_clip_range);  // :118
+  c.clip_hi = (float)(p->sensor_height - p->height_clip_range);  // :119
+  c.normal_cos = std::cos(p->normal_filter_thresh * M_PI / 180.0);  // :228
+  c.dist_thresh = p->ransac_distance_threshold;
+  c.log_prob = std::log(1.0 - p->ransac_probability);
+  c.max_iterations = p->ransac_max_iterations;
+  c.seed = p->seed;
+  return c;
+}
+
+struct FloorWork {
+  float4* filtered = nullptr;  // the RANSAC input {x, y, z, intensity}, input order (pf_a or pf_b)
+  float4* spare = nullptr;     // the other of the two
+  size_t n_clipped = 0, n_filtered = 0;
+  hgs_cloud* clipped = nullptr;  // the clipped cloud with its index (normal filter only); the caller frees it
+};
+
+// flags in pf_keep -> stable compaction of `in` into `out`; *m = the number kept (one read-back)
+int floor_compact(hgs_handle* h, const float4* in, size_t n, float4* out, size_t* m) {
+  int* d_count = h->pf_small.as<int>();
+  HGS_TRY(scan_u32(h, h->pf_keep.as<uint32_t>(), h->pf_slot.as<uint32_t>(), n));
+  launch_pf_compact(h->stream, in, (int)n, h->pf_keep.as<unsigned>(), h->pf_slot.as<unsigned>(), out, d_count);
+  HGS_HIP(h, hipGetLastError());
+  int* hs = h->h_small.as<int>();
+  HGS_HIP(h, hipMemcpyAsync(hs, d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  *m = (size_t)std::max(0, hs[0]);
+  return HGS_OK;
+}
+
+// clip + normal filter of steps 1 and 2; keep_clip / keep_normal / normals (host, may be null): the stage hook's outputs
+int floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, const FloorConsts& c, FloorWork* w, uint8_t* keep_clip, uint8_t* keep_normal, double* normals3) {
+  const size_t n = cloud->n_input;
+  const size_t cap = std::max<size_t>(n, 1);
+  HGS_HIP(h, h->pf_a.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_b.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_keep.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_slot.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_small.reserve(256));
+  HGS_HIP(h, h->h_small.reserve(256));
+  float4* all = h->pf_a.as<float4>();
+  float4* clipped = h->pf_b.as<float4>();
+  w->filtered = clipped, w->spare = all;
+  w->n_clipped = w->n_filtered = 0;
+  std::vector<uint32_t> flags;
+  if (keep_clip) std::memset(keep_clip, 0, n);
+  if (keep_normal) std::memset(keep_normal, 0, n);
+  if (normals3)
+    for (size_t i = 0; i < 3 * n; i++) normals3[i] = std::numeric_limits<double>::quiet_NaN();
+  if (n == 0) return HGS_OK;
+  launch_floor_clip_flags(h->stream, cloud->desc.raw, cloud->intensity, (int)n, c, all, h->pf_keep.as<unsigned>());
+  if (keep_clip || keep_normal || normals3) {
+    flags.resize(n);
+    HGS_HIP(h, hipMemcpyAsync(flags.data(), h->pf_keep.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  }
+  HGS_TRY(floor_compact(h, all, n, clipped, &w->n_clipped));
+  const size_t m = w->n_clipped;
+  w->n_filtered = m;
+  if (keep_clip)
+    for (size_t i = 0; i < n; i++) keep_clip[i] = flags[i] ? 1 : 0;
+  if (!p->use_normal_filtering) {
+    if (keep_normal)
+      for (size_t i = 0; i < n; i++) keep_normal[i] = flags[i] ? 1 : 0;
+    return HGS_OK;
+  }
+  if (m == 0) return HGS_OK;
+  // normal_filtering (:211-238): the clipped cloud gets a search index, k_knn_cov stages every point's fp64 neighbourhood covariance over its exact
+  // min(normal_k, n_clipped) nearest neighbours (itself included; a list of k slots never fills in a smaller cloud), k_floor_normal_flags takes the
+  // eigenvector of the smallest eigenvalue and tests it.  The viewpoint flip of pcl::NormalEstimation (:220) is irrelevant under |.| and not computed.
+  HGS_TRY(cloud_from_device(h, clipped, m, &w->clipped));
+  std::vector<hgs_cloud*> one{w->clipped};
+  HGS_TRY(ensure_index(h, one));
+  const int k = (int)std::min<size_t>((size_t)p->normal_k, m);
+  const int gather = h->knn_replay >= 0 ? h->knn_replay : 2;
+  int qpw = queries_per_wave(m, 32, h->knn_qpw_tiny, (size_t)h->knn_tiny_below);
+  if (qpw < 32 && (gather != 2 || k > 20)) qpw = 32;
+  HGS_HIP(h, h->cov_raw.reserve(m * 6 * sizeof(double)));
+  double* d_normals = nullptr;
+  if (normals3) {
+    HGS_HIP(h, h->pf_dist.reserve(m * 3 * sizeof(double)));
+    d_normals = h->pf_dist.as<double>();
+  }
+  const CloudDesc* d_descs = nullptr;
+  HGS_TRY(upload_descs(h, one, false, &d_descs, nullptr));
+  launch_knn_cov_raw(h->stream, d_descs, (int)m, k, qpw, gather, h->cov_raw.as<double>());
+  HGS_HIP(h, hipMemsetAsync(h->pf_keep.p, 0, m * sizeof(uint32_t), h->stream));
+  launch_floor_normal_flags(h->stream, w->clipped->desc, h->cov_raw.as<double>(), c, h->pf_keep.as<unsigned>(), d_normals);
+  std::vector<uint32_t> nflags;
+  std::vector<double> nrm;
+  if (keep_normal || normals3) {
+    nflags.resize(m);
+    HGS_HIP(h, hipMemcpyAsync(nflags.data(), h->pf_keep.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (normals3) {
+      nrm.resize(3 * m);
+      HGS_HIP(h, hipMemcpyAsync(nrm.data(), d_normals, 3 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  HGS_TRY(floor_compact(h, clipped, m, all, &w->n_filtered));
+  w->filtered = all, w->spare = clipped;
+  if (keep_normal || normals3) {
+    size_t j = 0;  // the j-th clipped point is the j-th input point with its clip flag set
+    for (size_t i = 0; i < n && j < m; i++) {
+      if (!flags[i]) continue;
+      if (keep_normal) keep_normal[i] = nflags[j] ? 1 : 0;
+      if (normals3) normals3[3 * i] = nrm[3 * j], normals3[3 * i + 1] = nrm[3 * j + 1], normals3[3 * i + 2] = nrm[3 * j + 2];
+      j++;
+    }
+  }
+  return HGS_OK;
+}
+
+// device work space of the RANSAC rounds inside h->misc: the state, one chunk's counts and planes
+struct FloorRansacBufs {
+  FloorRansacState* state;
+  int* counts;
+  double* planes;
+};
+int floor_ransac_bufs(hgs_handle* h, int chunk, FloorRansacBufs* b) {
+  const size_t o_counts = 256, o_planes = o_counts + align_up((size_t)chunk * sizeof(int), 256);
+  HGS_HIP(h, h->misc.reserve(o_planes + (size_t)chunk * 4 * sizeof(double)));
+  b->state = reinterpret_cast<FloorRansacState*>(h->misc.as<char>());
+  b->counts = reinterpret_cast<int*>(h->misc.as<char>() + o_counts);
+  b->planes = reinterpret_cast<double*>(h->misc.as<char>() + o_planes);
+  return HGS_OK;
+}
+
+int detect_floor_locked(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out, FloorWork& w) {
+  StageTimer tm(h, HGS_STAGE_PREFILTER);
+  const FloorConsts c = floor_consts(p);
+  HGS_TRY(floor_filter(h, cloud, p, c, &w, nullptr, nullptr, nullptr));
+  out->n_clipped = (uint32_t)w.n_clipped, out->n_filtered = (uint32_t)w.n_filtered;
+  const size_t nf = w.n_filtered;
+  if (filtered_out) HGS_TRY(cloud_from_device(h, w.filtered, nf, filtered_out));  // floor_filtered_pub (:127-130): published before the point-count test
+  if (nf == 0 || nf < (size_t)p->floor_pts_thresh) {  // :133 (an empty cloud / an empty clip range: not detected)
+    out->reason = HGS_FLOOR_TOO_FEW_POINTS;
+    return HGS_OK;
+  }
+  // RANSAC (:138-141) in rounds of `floor_chunk` hypotheses, driven like the engine's optimiser rounds: the decide kernel ticks the host-mapped
+  // progress mirror, the host stops enqueueing when it reads `done`, rounds that were queued behind it find the flag and return
+  const int chunk = std::max(1, std::min(kFloorMaxChunk, h->floor_chunk));
+  FloorRansacBufs b;
+  HGS_TRY(floor_ransac_bufs(h, chunk, &b));
+  std::vector<BatchLane> lanes(1);
+  lanes[0].stream = h->stream, lanes[0].b0 = 0, lanes[0].B = 1;
+  HGS_TRY(make_progress(h, 0, 1, &lanes[0].prog));
+  launch_floor_ransac_init(h->stream, b.state, c.max_iterations, lanes[0].prog);
+  const long max_rounds = ((long)c.max_iterations + chunk - 1) / chunk;
+  const float4* pts = w.filtered;
+  drive_lanes(
+      lanes, max_rounds,
+      [&](BatchLane& L) {
+        const int i0 = (int)L.round * chunk;
+        const int nh = std::min(chunk, c.max_iterations - i0);
+        launch_floor_ransac_planes(h->stream, pts, (int)nf, c.seed, i0, nh, b.state, b.planes, b.counts);
+        launch_floor_ransac_count(h->stream, pts, (int)nf, c.dist_thresh, b.planes, nh, b.state, b.counts);
+        launch_floor_ransac_decide(h->stream, b.counts, b.planes, i0, nh, (int)nf, c.max_iterations, c.log_prob, b.state, L.prog);
+      },
+      [&](BatchLane&) {});
+  // the model = the best plane rounded to float (no refinement: the reference never calls one); its inliers in order (:143-144)
+  launch_floor_inlier_flags(h->stream, pts, (int)nf, b.state, c.dist_thresh, h->pf_keep.as<unsigned>());
+  size_t n_in = 0;
+  HGS_TRY(floor_compact(h, pts, nf, w.spare, &n_in));
+  FloorRansacState st;
+  HGS_HIP(h, hipMemcpyAsync(&st, b.state, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  out->n_inliers = (uint32_t)n_in;
+  out->ransac_iterations = st.iterations;
+  float co[4] = {(float)st.plane[0], (float)st.plane[1], (float)st.plane[2], (float)st.plane[3]};
+  if (n_in < (size_t)p->floor_pts_thresh || st.best_i < 0) {  // :147
+    out->reason = HGS_FLOOR_TOO_FEW_INLIERS;
+    return HGS_OK;
+  }
+  // verticality (:152-161) against r = R^-1 e_z, then the upward flip (:164-166)
+  const double dot = (double)co[0] * c.nrx + (double)co[2] * c.nrz;
+  if (std::fabs(dot) < std::cos(p->floor_normal_thresh * M_PI / 180.0)) {
+    out->reason = HGS_FLOOR_NOT_VERTICAL;
+    return HGS_OK;
+  }
+  if (co[2] < 0.f)
+    for (float& v : co) v = -v;
+  for (int i = 0; i < 4; i++) out->coeffs[i] = co[i];
+  out->detected = 1, out->reason = HGS_FLOOR_DETECTED;
+  if (inliers_out) HGS_TRY(cloud_from_device(h, w.spare, n_in, inliers_out));  // floor_points_pub (:168-177)
+  return HGS_OK;
+}
+
+}  // namespace
+
+extern "C" int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out) try {
+  std::unique_lock<std::recursive_mutex> api_lock__;
+  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  if (filtered_out) *filtered_out = nullptr;
+  if (inliers_out) *inliers_out = nullptr;
+  if (!h || !cloud || !p || !out || cloud->owner != h || !floor_params_valid(p)) return HGS_ERR_INVALID_ARGUMENT;
+  HGS_TRY(set_device(h));
+  std::memset(out, 0, sizeof(*out));
+  FloorWork w;
+  const int rc = detect_floor_locked(h, cloud, p, out, filtered_out, inliers_out, w);
+  cloud_free(w.clipped);
+  if (rc != HGS_OK) {
+    if (filtered_out && *filtered_out) cloud_free(*filtered_out), *filtered_out = nullptr;
+    if (inliers_out && *inliers_out) cloud_free(*inliers_out), *inliers_out = nullptr;
+  }
+  return rc;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint8_t* keep_clip, uint8_t* keep_normal, double* normals3) try {
+  std::unique_lock<std::recursive_mutex> api_lock__;
+  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  if (!h || !cloud || !p || cloud->owner != h || !floor_params_valid(p)) return HGS_ERR_INVALID_ARGUMENT;
+  HGS_TRY(set_device(h));
+  FloorWork w;
+  const int rc = floor_filter(h, cloud, p, floor_consts(p), &w, keep_clip, keep_normal, normals3);
+  cloud_free(w.clipped);
+  return rc;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint32_t i0, uint32_t n, int32_t* counts, double* coeffs4) try {
+  std::unique_lock<std::recursive_mutex> api_lock__;
+  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  if (!h || !cloud || !p || cloud->owner != h || !floor_params_valid(p) || (n > 0 && !counts) || (uint64_t)i0 + n > 0x7fffffffull) return HGS_ERR_INVALID_ARGUMENT;
+  HGS_TRY(set_device(h));
+  const int chunk = std::max(1, std::min(kFloorMaxChunk, h->floor_chunk));
+  FloorRansacBufs b;
+  HGS_TRY(floor_ransac_bufs(h, chunk, &b));
+  const FloorConsts c = floor_consts(p);
+  const int np = (int)cloud->n_input;
+  for (uint32_t done = 0; done < n; done += (uint32_t)chunk) {
+    const int nh = (int)std::min<uint32_t>((uint32_t)chunk, n - done);
+    launch_floor_ransac_planes(h->stream, cloud->desc.raw, np, c.seed, (int)(i0 + done), nh, nullptr, b.planes, b.counts);
+    launch_floor_ransac_count(h->stream, cloud->desc.raw, np, c.dist_thresh, b.planes, nh, nullptr, b.counts);
+    HGS_HIP(h, hipGetLastError());
+    HGS_HIP(h, hipMemcpyAsync(counts + done, b.counts, (size_t)nh * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (coeffs4) HGS_HIP(h, hipMemcpyAsync(coeffs4 + 4 * (size_t)done, b.planes, (size_t)nh * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HGS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
 }

@@ -2814,6 +2814,153 @@ void launch_pf_to_cloud(hipStream_t s, const float4* in, int n, float4* raw, flo
                      desc ? desc_out : nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------ floor detection
+// FloorDetectionNodelet::detect (apps/floor_detection_nodelet.cpp:110-180; hgs_floor.h).  The clip and the normal filter are flag kernels in front of
+// the prefilter's scan + k_pf_compact; the normals come from k_knn_cov's staged fp64 neighbourhood covariances.  RANSAC is a dense counting problem:
+// a chunk of hypotheses (k_floor_ransac_planes) against every filtered point (k_floor_ransac_count), then one wave replays PCL's sequential rule
+// over the chunk's counts (k_floor_ransac_decide).  The counts are integers added with atomics: the result depends on neither grid nor chunk size.
+
+// the resident cloud as {x, y, z, intensity} records (what k_pf_compact and k_pf_to_cloud move) + the height clip's flags
+__global__ __launch_bounds__(kBlock) void k_floor_clip_flags(const float4* __restrict__ raw, const float* __restrict__ intensity, int n, FloorConsts c,
+                                                             float4* __restrict__ out, unsigned* __restrict__ keep) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = raw[i];
+  out[i] = make_float4(p.x, p.y, p.z, intensity[i]);
+  keep[i] = floor_clip_keep(c, p.x, p.y, p.z) ? 1u : 0u;
+}
+void launch_floor_clip_flags(hipStream_t s, const float4* raw, const float* intensity, int n, FloorConsts c, float4* out, unsigned* keep) {
+  if (n > 0) hipLaunchKernelGGL(k_floor_clip_flags, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, raw, intensity, n, c, out, keep);
+}
+
+// k_knn_cov in its staging mode only (REG 2: the fp64 neighbourhood covariance of sorted point i at raw_stage[6 i]), without k_cov_regularize behind it
+void launch_knn_cov_raw(hipStream_t s, const CloudDesc* descs, int max_n, int k, int qpw, int gather, double* raw_stage) {
+  if (max_n <= 0) return;
+  launch_knn_cov_g<2>(s, descs, 1, max_n, k, qpw, HGS_REG_NONE, gather, raw_stage, max_n);
+}
+
+// eigenvector, then flag: sorted point i of the clipped cloud writes the flag (and its normal) of its original position
+__global__ __launch_bounds__(kBlock) void k_floor_normal_flags(CloudDesc d, const double* __restrict__ raw_cov, FloorConsts c, unsigned* __restrict__ keep,
+                                                               double* __restrict__ normals) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= d.meta->nvalid) return;
+  const int o = __float_as_int(d.pts[i].w);
+  if (o < 0 || o >= d.n_input) return;
+  const double* r = raw_cov + 6 * (size_t)i;
+  double n3[3];
+  const bool k = floor_normal_keep(c, Sym3{r[0], r[1], r[2], r[3], r[4], r[5]}, n3);
+  keep[o] = k ? 1u : 0u;
+  if (normals) normals[3 * (size_t)o] = n3[0], normals[3 * (size_t)o + 1] = n3[1], normals[3 * (size_t)o + 2] = n3[2];
+}
+void launch_floor_normal_flags(hipStream_t s, CloudDesc d, const double* raw_cov, FloorConsts c, unsigned* keep, double* normals) {
+  if (d.n_input > 0) hipLaunchKernelGGL(k_floor_normal_flags, dim3((d.n_input + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d, raw_cov, c, keep, normals);
+}
+
+__global__ void k_floor_ransac_init(FloorRansacState* st, int max_iterations, Progress prog) {
+  if (threadIdx.x != 0) return;
+  prog.dev[0] = 0, prog.dev[1] = 0;
+  floor_ransac_init(*st, max_iterations);
+}
+void launch_floor_ransac_init(hipStream_t s, FloorRansacState* st, int max_iterations, Progress prog) {
+  hipLaunchKernelGGL(k_floor_ransac_init, dim3(1), dim3(64), 0, s, st, max_iterations, prog);
+}
+
+// hypotheses i0 .. i0 + nh - 1: their planes (all zero: degenerate) and a zeroed count each
+__global__ __launch_bounds__(kBlock) void k_floor_ransac_planes(const float4* __restrict__ pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st,
+                                                                double* __restrict__ planes, int* __restrict__ counts) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= nh || (st && st->done)) return;
+  counts[j] = 0;
+  double pl[4] = {0.0, 0.0, 0.0, 0.0};
+  if (n >= 3) {
+    unsigned a, b, c;
+    floor_sample3(seed, (unsigned)(i0 + j), (unsigned)n, &a, &b, &c);
+    floor_plane3(pts[a], pts[b], pts[c], pl);
+  }
+  planes[4 * j] = pl[0], planes[4 * j + 1] = pl[1], planes[4 * j + 2] = pl[2], planes[4 * j + 3] = pl[3];
+}
+void launch_floor_ransac_planes(hipStream_t s, const float4* pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st, double* planes, int* counts) {
+  if (nh > 0) hipLaunchKernelGGL(k_floor_ransac_planes, dim3((nh + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pts, n, seed, i0, nh, st, planes, counts);
+}
+
+// A block holds a tile of 256 points in registers and loops over kFloorHypPerBlock hypotheses of the chunk (blockIdx.y), whose coefficients are
+// wave-uniform (scalar loads); one ballot per wave and hypothesis, the four waves' counts meet in LDS, one global atomic per block and hypothesis.
+// Algorithmic work per chunk: n * nh plane evaluations (7 fp64 operations each) against 16 n bytes per hypothesis group: VALU bound.
+constexpr int kFloorHypPerBlock = 16;
+__global__ __launch_bounds__(kBlock) void k_floor_ransac_count(const float4* __restrict__ pts, int n, double thresh, const double* __restrict__ planes, int nh,
+                                                               const FloorRansacState* st, int* __restrict__ counts) {
+  if (st && st->done) return;  // (grid-uniform: a finished search costs a launch, no work)
+  __shared__ int s_cnt[kFloorHypPerBlock];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = i < n;
+  const float4 p = valid ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+  const int h0 = blockIdx.y * kFloorHypPerBlock;
+  const int hn = min(kFloorHypPerBlock, nh - h0);
+  if (threadIdx.x < kFloorHypPerBlock) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  for (int j = 0; j < hn; j++) {
+    const double* pl = planes + 4 * (size_t)(h0 + j);
+    if (pl[0] == 0.0 && pl[1] == 0.0 && pl[2] == 0.0) continue;  // a degenerate triple scores 0
+    const unsigned long long m = __ballot(valid && floor_within(pl, x, y, z, thresh));
+    if ((threadIdx.x & 63) == 0 && m != 0ull) atomicAdd(&s_cnt[j], __popcll(m));
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < hn && s_cnt[threadIdx.x] != 0) atomicAdd(&counts[h0 + threadIdx.x], s_cnt[threadIdx.x]);
+}
+void launch_floor_ransac_count(hipStream_t s, const float4* pts, int n, double thresh, const double* planes, int nh, const FloorRansacState* st, int* counts) {
+  if (n <= 0 || nh <= 0) return;
+  hipLaunchKernelGGL(k_floor_ransac_count, dim3((n + kBlock - 1) / kBlock, (nh + kFloorHypPerBlock - 1) / kFloorHypPerBlock), dim3(kBlock), 0, s, pts, n, thresh,
+                     planes, nh, st, counts);
+}
+
+// One wave replays the sequential rule over the chunk's counts in hypothesis order (64 counts per load, handed round with v_readlane; every lane
+// holds the same state): hypotheses from the stopping index on are ignored, and the chunk that reaches it sets `done`.
+__global__ __launch_bounds__(64) void k_floor_ransac_decide(const int* __restrict__ counts, const double* __restrict__ planes, int i0, int nh, int n, int max_iterations,
+                                                            double log_prob, FloorRansacState* st, Progress prog) {
+  const int lane = (int)(threadIdx.x & 63);
+  FloorRansacState s = *st;
+  bool finished_now = false;
+  if (!s.done) {
+    for (int off = 0; off < nh && !s.done; off += 64) {
+      const int mine = off + lane < nh ? counts[off + lane] : 0;
+      const int m = min(64, nh - off);
+      for (int j = 0; j < m; j++) {
+        const int i = i0 + off + j;
+        if (!floor_ransac_goes_on(s, i, max_iterations)) {
+          s.done = 1;
+          break;
+        }
+        const int cnt = __builtin_amdgcn_readlane(mine, j);
+        if (floor_ransac_step(s, i, cnt, n, log_prob)) {
+          const double* pl = planes + 4 * (size_t)(off + j);
+          s.plane[0] = pl[0], s.plane[1] = pl[1], s.plane[2] = pl[2], s.plane[3] = pl[3];
+        }
+      }
+    }
+    if (!s.done && !floor_ransac_goes_on(s, i0 + nh, max_iterations)) s.done = 1;
+    finished_now = s.done != 0;
+    if (lane == 0) *st = s;
+  }
+  if (lane == 0) progress_tick(prog, finished_now);
+}
+void launch_floor_ransac_decide(hipStream_t s, const int* counts, const double* planes, int i0, int nh, int n, int max_iterations, double log_prob, FloorRansacState* st,
+                                Progress prog) {
+  hipLaunchKernelGGL(k_floor_ransac_decide, dim3(1), dim3(64), 0, s, counts, planes, i0, nh, n, max_iterations, log_prob, st, prog);
+}
+
+// the inliers of the chosen model — the best plane's coefficients rounded to float — as flags for the scan + k_pf_compact
+__global__ __launch_bounds__(kBlock) void k_floor_inlier_flags(const float4* __restrict__ pts, int n, const FloorRansacState* st, double thresh, unsigned* __restrict__ keep) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double pl[4] = {(double)(float)st->plane[0], (double)(float)st->plane[1], (double)(float)st->plane[2], (double)(float)st->plane[3]};
+  const float4 p = pts[i];
+  keep[i] = (st->best_i >= 0 && floor_within(pl, (double)p.x, (double)p.y, (double)p.z, thresh)) ? 1u : 0u;
+}
+void launch_floor_inlier_flags(hipStream_t s, const float4* pts, int n, const FloorRansacState* st, double thresh, unsigned* keep) {
+  if (n > 0) hipLaunchKernelGGL(k_floor_inlier_flags, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pts, n, st, thresh, keep);
+}
+
 }  // namespace hgs
 
 // ------------------------------------------------------------------------------------------------ stage-level test hooks

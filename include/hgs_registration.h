@@ -259,6 +259,52 @@ int hgs_cloud_download(hgs_cloud* c, void* out_pts, size_t stride_bytes);
  * may be up to 21 levels deep (2^21 voxels per axis: 0.01 m over 20 km); HGS_ERR_INVALID_ARGUMENT beyond that. */
 int hgs_map_cloud_generate(hgs_handle* h, hgs_cloud* const* keyframes, const float* poses, size_t n_keyframes, double resolution, hgs_cloud** out);
 
+/* ---- row 12: FloorDetectionNodelet::detect (apps/floor_detection_nodelet.cpp:110-238) ------------------------------------ */
+/* Height clip -> normal filter -> RANSAC plane -> acceptance tests, on the device, on a resident cloud (what hgs_prefilter returned goes in without a
+ * download: the nodelet subscribes to /filtered_points, :44).  Parameters: the nodelet's rosparams (:57-63) and the constants of :140 / :219 and of
+ * pcl::RandomSampleConsensus.
+ * Deviations from PCL, stated: the hypothesis sequence is a counter-based generator of ours, a pure function of (seed, i, n_filtered)
+ * (PCL draws from a boost::mt19937 shuffle); a degenerate triple counts as an iteration (PCL redraws); plane and distance arithmetic is fp64 (PCL: float);
+ * the neighbourhood covariance of the normals is centred fp64 (PCL: a float covariance whose form differs between PCL versions); with tilt_deg != 0 the
+ * filtered points keep the input's own bits (PCL rotates there and back in float).  With tilt_deg = 0 the clip is bit-exact PCL.  There is no least-squares
+ * refinement of the model (the reference never calls one). */
+enum hgs_floor_reason {
+  HGS_FLOOR_DETECTED = 0,
+  HGS_FLOOR_TOO_FEW_POINTS = 1,  /* n_filtered < floor_pts_thresh (:133); also an empty cloud / nothing inside the clip range */
+  HGS_FLOOR_TOO_FEW_INLIERS = 2, /* n_inliers < floor_pts_thresh (:147)                                                    */
+  HGS_FLOOR_NOT_VERTICAL = 3     /* |n . r| < cos(floor_normal_thresh) (:152-161)                                          */
+};
+typedef struct hgs_floor_params {
+  double tilt_deg;                  /* tilt_deg              (0.0)   :57                                       */
+  double sensor_height;             /* sensor_height         (2.0)   :58                                       */
+  double height_clip_range;         /* height_clip_range     (1.0)   :59                                       */
+  int32_t floor_pts_thresh;         /* floor_pts_thresh      (512)   :60                                       */
+  int32_t use_normal_filtering;     /* use_normal_filtering  (true)  :62                                       */
+  double floor_normal_thresh;       /* floor_normal_thresh   (10.0)  :61  [deg]                                */
+  double normal_filter_thresh;      /* normal_filter_thresh  (20.0)  :63  [deg]                                */
+  int32_t normal_k;                 /* ne.setKSearch         (10)    :219, 3..64                               */
+  int32_t ransac_max_iterations;    /* pcl::SampleConsensus max_iterations_ (1000)                             */
+  double ransac_distance_threshold; /* ransac.setDistanceThreshold (0.1) :140                                  */
+  double ransac_probability;        /* pcl::SampleConsensus probability_    (0.99), inside (0, 1)              */
+  uint32_t seed;                    /* of the hypothesis generator (0)                                         */
+  int32_t reserved;
+} hgs_floor_params;
+typedef struct hgs_floor_result {
+  float coeffs[4];           /* the floor plane a x + b y + c z + d = 0, normal upward (:164-166); zeros without a model   */
+  int32_t detected;          /* 1: boost::optional has a value                                                             */
+  int32_t reason;            /* hgs_floor_reason                                                                           */
+  uint32_t n_clipped;        /* points inside the height clip                                                              */
+  uint32_t n_filtered;       /* ... that also pass the normal filter (== n_clipped without it): the RANSAC input           */
+  uint32_t n_inliers;        /* filtered points within the threshold of the model                                          */
+  int32_t ransac_iterations; /* hypotheses evaluated                                                                       */
+} hgs_floor_result;
+int hgs_floor_params_default(hgs_floor_params* p);
+/* *filtered_out (NULL ok): the RANSAC input as a resident cloud, what floor_filtered_pub publishes (:127-130) — set whenever the call returns HGS_OK;
+ * *inliers_out (NULL ok): the model's inliers in order, what floor_points_pub publishes (:168-177) — set when a floor was detected, else NULL.
+ * Both belong to `h` and are the caller's to destroy.  HGS_ERR_INVALID_ARGUMENT: negative thresholds, normal_k outside 3..64, ransac_probability outside
+ * (0, 1), non-finite parameters, a cloud of another handle.  The work is accounted under HGS_STAGE_PREFILTER. */
+int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out);
+
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 enum hgs_stage {
   HGS_STAGE_UPLOAD = 0,     /* H2D + pack                                            */
@@ -269,7 +315,7 @@ enum hgs_stage {
   HGS_STAGE_ERROR = 5,      /* LM trial error evaluation                             */
   HGS_STAGE_SOLVE = 6,      /* 6x6 reductions + solve + LM/Newton update (ICP: Umeyama step) */
   HGS_STAGE_FITNESS = 7,    /* fitness score NN pass                                 */
-  HGS_STAGE_PREFILTER = 8,  /* distance filter + voxel grid + outlier removal        */
+  HGS_STAGE_PREFILTER = 8,  /* distance filter + voxel grid + outlier removal; map cloud; floor detection */
   HGS_STAGE_COUNT = 9
 };
 /* Enable/disable hipEvent bracketing of every kernel stage on the handle's stream (adds sync cost when read). */
@@ -295,6 +341,13 @@ int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17
  * (DBL_MAX when no step was taken).  Needs a source (the kernel takes its tile count from it: HGS_ERR_NO_SOURCE), no target. */
 int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_in[12], double mse_prev, int32_t iterations_in,
                        double T12_out[12], int32_t flags3[3] /* converged, done, iterations */, double* mse);
+/* Floor detection, the two filters: per point of `cloud` (original order) keep_clip[i] / keep_normal[i] = 1 when it passes the height clip / the clip
+ * and the normal filter (without use_normal_filtering: equal to keep_clip), and normals3[3 i ..] its fp64 unit normal (NaN for a point outside the clip
+ * or without use_normal_filtering).  Any of the three may be NULL. */
+int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint8_t* keep_clip, uint8_t* keep_normal, double* normals3);
+/* Floor detection, the RANSAC counting step (k_floor_ransac_planes + k_floor_ransac_count) with `cloud` taken as the filtered set: counts[j] and
+ * coeffs4[4 j ..] (fp64 plane, zeros for a degenerate triple) of hypotheses i0 .. i0 + n - 1 under p->seed and p->ransac_distance_threshold. */
+int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint32_t i0, uint32_t n, int32_t* counts, double* coeffs4);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
 /* One NDT derivative pass at p = (tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */
@@ -306,7 +359,7 @@ int hgs_debug_merge_shard_records(const hgs_result* gathered, const int32_t* cou
                                   hgs_result* all_out, int32_t* duplicate_id);
 /* A measurement / test knob of one engine: "batch_lanes", "lane_start", "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
  * "seed_grid", "knn_replay", "ndt_resident", "ndt_chunk", "hilbert_levels", "nn_qpw", "nn_qpw16_below", "nn_qpw32_below", "fused_rounds", "fused_rounds_below", "fused_rounds_max_problems", "fused_rounds_max_blocks", "early_result", "early_run_ahead",
- * "knn_tiny_below", "upload_trace", "prefilter_fast".  Results never depend on them (the tests
+ * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096).  Results never depend on them (the tests
  * that force a code path check exactly that); A/B runs and those tests are the only callers — the library reads no tuning variable from the environment. */
 int hgs_debug_set_option(hgs_handle* h, const char* key, int32_t value);
 
