@@ -29,7 +29,9 @@
 
 #include "../../include/hgs_registration.h"
 #include "hgs_comm.h"
+#include "hgs_consts.h"
 #include "hgs_device.h"
+#include "hgs_resources.h"
 #include "hgs_sort.h"
 
 using namespace hgs;
@@ -38,210 +40,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct DeviceBuffer {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-struct PinnedBuffer {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-// Small host -> device uploads (cloud descriptors, guesses, work plans) go through a ring of pinned slots, each guarded by an event recorded
-// behind its copy: a slot is rewritten only after the copy that read it has completed, so no caller has to synchronise the stream just to make a
-// staging buffer reusable (rounds 1-4 did, once per index build, once per covariance pass, once per NDT plan: 15-30 us of host latency each on
-// the single-registration path).
-struct PinnedRing {
-  static constexpr int kSlots = 8;
-  PinnedBuffer buf[kSlots];
-  hipEvent_t ev[kSlots] = {};
-  bool pending[kSlots] = {};
-  int next = 0;
-  // a slot of at least `bytes` whose previous upload has completed; *slot identifies it for commit()
-  hipError_t stage(size_t bytes, void** host, int* slot) {
-    const int k = next;
-    next = (next + 1) % kSlots;
-    if (pending[k]) {
-      const hipError_t e = hipEventSynchronize(ev[k]);
-      if (e != hipSuccess) return e;
-      pending[k] = false;
-    }
-    const hipError_t e = buf[k].reserve(bytes);
-    if (e != hipSuccess) return e;
-    *host = buf[k].p, *slot = k;
-    return hipSuccess;
-  }
-  // the copy out of the slot has been enqueued on `stream`
-  hipError_t commit(int slot, hipStream_t stream) {
-    if (!ev[slot]) {
-      const hipError_t e = hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming);
-      if (e != hipSuccess) return e;
-    }
-    const hipError_t e = hipEventRecord(ev[slot], stream);
-    if (e == hipSuccess) pending[slot] = true;
-    return e;
-  }
-  // H2D of `bytes` from `src` (any host memory) to `dst` through a slot
-  hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t stream) {
-    void* host = nullptr;
-    int slot = 0;
-    hipError_t e = stage(bytes, &host, &slot);
-    if (e != hipSuccess) return e;
-    std::memcpy(host, src, bytes);
-    e = hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return e;
-    return commit(slot, stream);
-  }
-  void release() {
-    for (int k = 0; k < kSlots; k++) {
-      if (ev[k]) (void)hipEventDestroy(ev[k]);
-      ev[k] = nullptr, pending[k] = false;
-      buf[k].release();
-    }
-  }
-};
-
-// A few helper threads that pack point records next to the calling thread (upload_points_packed).  One core packs a cold 119 k-point sweep (3.8 MB
-// read, 1.9 MB written) in 150 us; kWorkers + 1 threads in 59 us (same box, scripts/probes/upload_probe.py: hgs_set_source 0.164 -> 0.075 ms of a
-// 0.39 ms odometry step).  The workers only touch host memory (no HIP call); they sleep on a condition variable between uploads and are joined by
-// hgs_destroy.
-struct PackPool {
-  static constexpr int kWorkers = 3;
-  struct Job {
-    const char* src = nullptr;
-    float* dst = nullptr;
-    size_t n = 0, stride = 0, chunk = 0, nchunks = 0;
-    bool has_intensity = false;
-    bool scatter = false;  // false: pack strided records at src into float4 at dst (upload); true: scatter float4 at src into strided records at dst (hgs_transform_source)
-    std::atomic<size_t> next{0};
-    std::atomic<unsigned char>* ready = nullptr;  // [nchunks]
-  };
-  std::vector<std::thread> threads;
-  std::mutex m;
-  std::condition_variable cv;
-  Job* job = nullptr;   // guarded by m
-  unsigned long generation = 0;
-  int active = 0;       // workers inside the current job
-  bool stop = false;
-
-  static void pack_chunk(const Job& j, size_t c) {
-    const size_t i0 = c * j.chunk, m = std::min(j.chunk, j.n - i0);
-    if (j.scatter) {  // x, y, z (and data[3] = 1 when the record has room for it) of the caller's records; everything else in them is left alone
-      const float* s4 = reinterpret_cast<const float*>(j.src) + 4 * i0;
-      char* o = reinterpret_cast<char*>(j.dst) + i0 * j.stride;
-      for (size_t i = 0; i < m; i++) {
-        float* f = reinterpret_cast<float*>(o + i * j.stride);
-        f[0] = s4[4 * i], f[1] = s4[4 * i + 1], f[2] = s4[4 * i + 2];
-        if (j.stride >= 16) f[3] = 1.0f;
-      }
-      j.ready[c].store(1, std::memory_order_release);
-      return;
-    }
-    const char* s0 = j.src + i0 * j.stride;
-    float* dst = j.dst + 4 * i0;
-    if (j.has_intensity) {
-      for (size_t i = 0; i < m; i++) {
-        const float* f = reinterpret_cast<const float*>(s0 + i * j.stride);
-        dst[4 * i] = f[0], dst[4 * i + 1] = f[1], dst[4 * i + 2] = f[2], dst[4 * i + 3] = f[4];
-      }
-    } else {
-      for (size_t i = 0; i < m; i++) {
-        const float* f = reinterpret_cast<const float*>(s0 + i * j.stride);
-        dst[4 * i] = f[0], dst[4 * i + 1] = f[1], dst[4 * i + 2] = f[2], dst[4 * i + 3] = 0.f;
-      }
-    }
-    j.ready[c].store(1, std::memory_order_release);
-  }
-  // takes chunks until none is left; false if there was none
-  static bool help(Job& j) {
-    const size_t c = j.next.fetch_add(1, std::memory_order_relaxed);
-    if (c >= j.nchunks) return false;
-    pack_chunk(j, c);
-    return true;
-  }
-  void worker() {
-    unsigned long seen = 0;
-    for (;;) {
-      Job* j = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return stop || (job && generation != seen); });
-        if (stop) return;
-        seen = generation, j = job, active++;
-      }
-      while (help(*j)) {
-      }
-      {
-        std::lock_guard<std::mutex> lk(m);
-        active--;
-      }
-      cv.notify_all();
-    }
-  }
-  void post(Job* j) {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      if (threads.empty())
-        for (int i = 0; i < kWorkers; i++) threads.emplace_back([this] { worker(); });
-      job = j, generation++;
-    }
-    cv.notify_all();
-  }
-  // the job's memory may go away after this: no worker is inside it, none will enter it
-  void retire() {
-    std::unique_lock<std::mutex> lk(m);
-    job = nullptr;
-    cv.wait(lk, [&] { return active == 0; });
-  }
-  void shutdown() {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      stop = true;
-    }
-    cv.notify_all();
-    for (std::thread& t : threads) t.join();
-    threads.clear();
-  }
-};
 
 int next_pow2(int v) {
   int p = 1;
@@ -252,12 +50,21 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
+// A voxel hash table of a cloud in the target role: open addressing over cell keys, the cells' records behind it, all in one block.
+struct VoxelTable {
+  DeviceBuffer block;
+  int* hash_keys = nullptr;
+  int* hash_vals = nullptr;
+  int2* hash_kv = nullptr;  // {key, value} packed per slot (NDT: k_ndt_pack_hash); null where nothing reads it (VGICP)
+  NdtCellRec* cells = nullptr;
+  int hash_cap = 0;
+};
+
 struct hgs_cloud {
   hgs_handle* owner = nullptr;
   size_t n_input = 0;
   int P = 1;
-  void* block = nullptr;
-  size_t block_bytes = 0;
+  DeviceBuffer block;
   CloudDesc desc{};
   CloudDesc* dev_desc = nullptr;  // the descriptor inside the cloud's block (pad = 1, sort_off = 0), written by the kernel that fills raw[]: upload_descs of ONE cloud returns it
   float* intensity = nullptr;  // [n_input] PointXYZI intensity (what hgs_cloud_download / the prefilter hand back)
@@ -269,28 +76,16 @@ struct hgs_cloud {
   bool has_ndt = false;
   double ndt_resolution = 0;
   int ndt_min_points = 0;
-  void* ndt_block = nullptr;
-  size_t ndt_block_bytes = 0;
-  int* ndt_hash_keys = nullptr;
-  int* ndt_hash_vals = nullptr;
-  NdtCellRec* ndt_cells = nullptr;
-  int2* ndt_hash_kv = nullptr;
-  int ndt_hash_cap = 0;
+  VoxelTable ndt;
   // VGICP Gaussian voxel map (target role)
   bool has_vg = false;
   double vg_resolution = 0;
   int vg_cov_k = 0;
-  void* vg_block = nullptr;
-  size_t vg_block_bytes = 0;
+  VoxelTable vg;
   // seed grid (target role of the 1-NN kernels: seed_grid_lookup, hgs_kernels.hip)
   bool has_seed = false;
-  void* seed_block = nullptr;
-  size_t seed_block_bytes = 0;
+  DeviceBuffer seed_block;
   int seed_bits = 0;
-  int* vg_hash_keys = nullptr;
-  int* vg_hash_vals = nullptr;
-  NdtCellRec* vg_cells = nullptr;
-  int vg_hash_cap = 0;
 };
 
 struct ProfEvent {
@@ -374,7 +169,7 @@ struct hgs_handle {
 
   // freed cloud blocks kept for reuse: the odometry path creates and destroys one cloud per sweep, and hipMalloc /
   // hipFree (which synchronises the device) cost more than the upload itself
-  std::vector<std::pair<void*, size_t>> block_pool;
+  std::vector<DeviceBuffer> block_pool;
   // every cloud this engine has created and not yet destroyed: hgs_destroy orphans them (frees their device memory, clears
   // `owner`) so that a later hgs_cloud_destroy / hgs_cloud_download on a cached pointer is safe instead of a use-after-free
   std::vector<hgs_cloud*> live_clouds;
@@ -388,6 +183,16 @@ struct hgs_handle {
   std::vector<ProfEvent> prof_free;
   double prof_ms[HGS_STAGE_COUNT];
   uint64_t prof_launches[HGS_STAGE_COUNT];
+
+  hgs_handle() = default;
+  hgs_handle(const hgs_handle&) = delete;
+  hgs_handle& operator=(const hgs_handle&) = delete;
+  void synchronize_streams() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipStream_t ls : lane_stream)
+      if (ls) (void)hipStreamSynchronize(ls);
+  }
+  ~hgs_handle();
 };
 
 namespace {
@@ -429,6 +234,16 @@ struct StageTimer {
     (void)hipEventRecord(ev.b, h->stream);
     h->prof_events.push_back(ev);
   }
+};
+
+// One call at a time per engine (hgs_handle::api_mutex): what every locking entry point opens with.  A null engine, and a cloud that is null or has
+// outlived its engine, lock nothing — the entry point rejects them (or frees the orphan) right behind this.
+struct ApiLock {
+  std::unique_lock<std::recursive_mutex> lk;
+  explicit ApiLock(hgs_handle* h) {
+    if (h) lk = std::unique_lock<std::recursive_mutex>(h->api_mutex);
+  }
+  explicit ApiLock(hgs_cloud* c) : ApiLock(c ? c->owner : nullptr) {}
 };
 
 int set_device(hgs_handle* h) {
@@ -535,23 +350,21 @@ int cloud_alloc(hgs_handle* h, size_t n, hgs_cloud** out) {
   off = align_up(off + slots * sizeof(int), 256);
   const size_t o_int = off;
   off = align_up(off + n_cap * sizeof(float), 256);
-  c->block_bytes = off;
   hipError_t e = hipSuccess;
   for (size_t k = 0; k < h->block_pool.size(); k++) {
-    if (h->block_pool[k].second >= off && h->block_pool[k].second <= 2 * off + (1u << 20)) {
-      c->block = h->block_pool[k].first;
-      c->block_bytes = h->block_pool[k].second;
+    if (h->block_pool[k].cap >= off && h->block_pool[k].cap <= 2 * off + (1u << 20)) {
+      c->block = std::move(h->block_pool[k]);
       h->block_pool.erase(h->block_pool.begin() + k);
       break;
     }
   }
-  if (!c->block) e = hipMalloc(&c->block, off);
+  if (!c->block.p) e = c->block.alloc(off);
   if (e != hipSuccess) {
     h->err = std::string("hipMalloc(cloud) failed: ") + hipGetErrorString(e);
     delete c;
     return HGS_ERR_HIP;
   }
-  char* base = (char*)c->block;
+  char* base = c->block.as<char>();
   c->desc.meta = (CloudMeta*)(base + o_meta);
   c->dev_desc = (CloudDesc*)(base + o_desc);
   c->desc.raw = (const float4*)(base + o_raw);
@@ -573,16 +386,10 @@ int cloud_alloc(hgs_handle* h, size_t n, hgs_cloud** out) {
 
 // Releases the device memory of a cloud (the struct itself stays): what hgs_destroy does to clouds that outlive their engine.
 void cloud_release_device(hgs_cloud* c, bool pool) {
-  if (c->block) {
-    // stream order makes reuse safe: every kernel that touches the block was enqueued on the owner's stream
-    hgs_handle* h = c->owner;
-    if (pool && h && h->block_pool.size() < 6) h->block_pool.emplace_back(c->block, c->block_bytes);
-    else (void)hipFree(c->block);
-  }
-  if (c->ndt_block) (void)hipFree(c->ndt_block);
-  if (c->vg_block) (void)hipFree(c->vg_block);
-  if (c->seed_block) (void)hipFree(c->seed_block);
-  c->block = nullptr, c->ndt_block = nullptr, c->vg_block = nullptr, c->seed_block = nullptr;
+  // stream order makes reuse safe: every kernel that touches the block was enqueued on the owner's stream
+  hgs_handle* h = c->owner;
+  if (c->block.p && pool && h && h->block_pool.size() < 6) h->block_pool.push_back(std::move(c->block));
+  c->block.release(), c->ndt.block.release(), c->vg.block.release(), c->seed_block.release();
   c->has_index = c->has_cov = c->has_ndt = c->has_vg = c->has_seed = false;
 }
 
@@ -650,6 +457,49 @@ int queries_per_wave(size_t total_queries, int small, int tiny = 0, size_t tiny_
   return total_queries >= (size_t)600000 ? 64 : small;
 }
 
+// ---- rocPRIM on the engine's stream: size query, work space in sort_tmp, the call ----------------------------
+int scan_u32(hgs_handle* h, const uint32_t* in, uint32_t* out, size_t n) {
+  size_t tmp = 0;
+  if (hgs_exclusive_scan_u32(nullptr, &tmp, in, out, n, h->stream) != 0) {
+    h->err = "rocprim exclusive_scan (size query) failed";
+    return HGS_ERR_HIP;
+  }
+  HGS_HIP(h, h->sort_tmp.reserve(tmp));
+  if (hgs_exclusive_scan_u32(h->sort_tmp.p, &tmp, in, out, n, h->stream) != 0) {
+    h->err = "rocprim exclusive_scan failed";
+    return HGS_ERR_HIP;
+  }
+  return HGS_OK;
+}
+
+// room for n key / value pairs in both halves of the sort's double buffer
+int reserve_sort_pairs(hgs_handle* h, size_t n) {
+  for (int i = 0; i < 2; i++) {
+    HGS_HIP(h, h->sort_keys[i].reserve(n * sizeof(uint64_t)));
+    HGS_HIP(h, h->sort_vals[i].reserve(n * sizeof(uint32_t)));
+  }
+  return HGS_OK;
+}
+
+// stable radix sort of sort_keys[0] / sort_vals[0] into sort_keys[1] / sort_vals[1] by key bits [begin_bit, end_bit)
+int sort_pairs(hgs_handle* h, size_t n, int begin_bit, int end_bit) {
+  auto sort = [&](void* tmp, size_t* tmp_bytes) {
+    return hgs_sort_pairs_u64_u32(tmp, tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
+                                  h->sort_vals[1].as<uint32_t>(), n, begin_bit, end_bit, h->stream);
+  };
+  size_t tmp_bytes = 0;
+  if (sort(nullptr, &tmp_bytes) != 0) {
+    h->err = "rocprim radix_sort_pairs (size query) failed";
+    return HGS_ERR_HIP;
+  }
+  HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
+  if (sort(h->sort_tmp.p, &tmp_bytes) != 0) {
+    h->err = "rocprim radix_sort_pairs failed";
+    return HGS_ERR_HIP;
+  }
+  return HGS_OK;
+}
+
 // Build the search index (Hilbert sort + implicit tree) of every cloud in the list that lacks one — one
 // batched kernel sequence and ONE radix sort for the whole list.
 int ensure_index(hgs_handle* h, const std::vector<hgs_cloud*>& all) {
@@ -671,30 +521,14 @@ int ensure_index(hgs_handle* h, const std::vector<hgs_cloud*>& all) {
     const int nc = (int)chunk.size();
     // meta (nvalid, bbox) was filled at upload time
     if (total > 0) {
-      for (int i = 0; i < 2; i++) {
-        HGS_HIP(h, h->sort_keys[i].reserve(total * sizeof(uint64_t)));
-        HGS_HIP(h, h->sort_vals[i].reserve(total * sizeof(uint32_t)));
-      }
+      HGS_TRY(reserve_sort_pairs(h, total));
       // The sort compares the top `hilbert_levels` levels of the curve (3 bits each) + the cloud ordinal: points that share a cell of the finest
       // compared level stay in input order (stable sort), i.e. in firing order — still neighbours.  Fewer compared bits = fewer radix passes.
       const int drop_bits = 3 * (16 - h->hilbert_levels);
       launch_hilbert_keys(h->stream, d_descs, nc, max_n, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>(), drop_bits);
       int bits = 48;
       for (int v = nc - 1; v > 0; v >>= 1) bits++;
-      size_t tmp_bytes = 0;
-      int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                      h->sort_vals[1].as<uint32_t>(), total, drop_bits, bits, h->stream);
-      if (rc != 0) {
-        h->err = "rocprim radix_sort_pairs (size query) failed";
-        return HGS_ERR_HIP;
-      }
-      HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-      rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                  h->sort_vals[1].as<uint32_t>(), total, drop_bits, bits, h->stream);
-      if (rc != 0) {
-        h->err = "rocprim radix_sort_pairs failed";
-        return HGS_ERR_HIP;
-      }
+      HGS_TRY(sort_pairs(h, total, drop_bits, bits));
     }
     launch_gather_sorted(h->stream, d_descs, nc, max_P * kLeaf, h->sort_vals[1].as<unsigned>());
     launch_build_tree(h->stream, d_descs, nc, max_P);
@@ -739,55 +573,47 @@ int ensure_cov(hgs_handle* h, const std::vector<hgs_cloud*>& all, int k) {
   return HGS_OK;
 }
 
+// The voxel table of `c` for `cap` hash slots and up to `max_cells` cells, built from sorted cell keys: (re)allocated when the capacity changed, its keys
+// cleared; `grid_params`, `cell_keys(keys, vals)` and `build_cells(sorted keys, sorted vals)` are the method's own launches, in that order around the sort.
+template <typename P, typename K, typename C>
+int build_voxel_table(hgs_handle* h, const hgs_cloud* c, VoxelTable& t, int cap, int max_cells, bool packed, P&& grid_params, K&& cell_keys, C&& build_cells) {
+  const size_t n = c->n_input;
+  if (!t.block.p || t.hash_cap != cap) {
+    const size_t o_keys = 0, o_vals = align_up((size_t)cap * 4, 256), o_kv = o_vals + align_up((size_t)cap * 4, 256);
+    const size_t o_cells = o_kv + (packed ? align_up((size_t)cap * 8, 256) : 0);
+    HGS_HIP(h, t.block.alloc(o_cells + (size_t)max_cells * sizeof(NdtCellRec)));
+    char* base = t.block.as<char>();
+    t.hash_keys = (int*)(base + o_keys);
+    t.hash_vals = (int*)(base + o_vals);
+    t.hash_kv = packed ? (int2*)(base + o_kv) : nullptr;
+    t.cells = (NdtCellRec*)(base + o_cells);
+    t.hash_cap = cap;
+  }
+  HGS_HIP(h, hipMemsetAsync(t.hash_keys, 0xff, (size_t)cap * 4, h->stream));
+  grid_params();
+  if (n > 0) {
+    HGS_TRY(reserve_sort_pairs(h, n));
+    cell_keys(h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>());
+    HGS_TRY(sort_pairs(h, n, 0, 32));
+    build_cells(h->sort_keys[1].as<unsigned long long>(), h->sort_vals[1].as<unsigned>());
+  }
+  return HGS_OK;
+}
+
 int ensure_ndt_target(hgs_handle* h, hgs_cloud* c) {
   const double res = h->prm.resolution;
   const int min_pts = h->prm.ndt_min_points_per_voxel;
   if (c->has_ndt && c->ndt_resolution == res && c->ndt_min_points == min_pts) return HGS_OK;
   StageTimer tm(h, HGS_STAGE_VOXELIZE);
-  const size_t n = c->n_input;
-  const int max_cells = (int)(n / (size_t)std::max(1, min_pts)) + 1;
+  const int max_cells = (int)(c->n_input / (size_t)std::max(1, min_pts)) + 1;
   const int cap = next_pow2(std::max(64, 4 * max_cells));
-  if (!c->ndt_block || c->ndt_hash_cap != cap) {
-    if (c->ndt_block) (void)hipFree(c->ndt_block);
-    c->ndt_block = nullptr;
-    const size_t o_keys = 0, o_vals = align_up((size_t)cap * 4, 256), o_kv = o_vals + align_up((size_t)cap * 4, 256);
-    const size_t o_cells = o_kv + align_up((size_t)cap * 8, 256);
-    const size_t bytes = o_cells + (size_t)max_cells * sizeof(NdtCellRec);
-    HGS_HIP(h, hipMalloc(&c->ndt_block, bytes));
-    c->ndt_block_bytes = bytes;
-    c->ndt_hash_keys = (int*)((char*)c->ndt_block + o_keys);
-    c->ndt_hash_vals = (int*)((char*)c->ndt_block + o_vals);
-    c->ndt_hash_kv = (int2*)((char*)c->ndt_block + o_kv);
-    c->ndt_cells = (NdtCellRec*)((char*)c->ndt_block + o_cells);
-    c->ndt_hash_cap = cap;
-  }
-  HGS_HIP(h, hipMemsetAsync(c->ndt_hash_keys, 0xff, (size_t)cap * 4, h->stream));
   const float inv_leaf = 1.0f / (float)res;
-  launch_ndt_grid_params(h->stream, c->desc, inv_leaf);
-  if (n > 0) {
-    for (int i = 0; i < 2; i++) {
-      HGS_HIP(h, h->sort_keys[i].reserve(n * sizeof(uint64_t)));
-      HGS_HIP(h, h->sort_vals[i].reserve(n * sizeof(uint32_t)));
-    }
-    launch_ndt_cell_keys(h->stream, c->desc, inv_leaf, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>());
-    size_t tmp_bytes = 0;
-    int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                    h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs (size query) failed";
-      return HGS_ERR_HIP;
-    }
-    HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-    rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs failed";
-      return HGS_ERR_HIP;
-    }
-    launch_ndt_build_cells(h->stream, c->desc, h->sort_keys[1].as<unsigned long long>(), h->sort_vals[1].as<unsigned>(), min_pts, c->ndt_hash_keys,
-                           c->ndt_hash_vals, cap - 1, c->ndt_cells);
-  }
-  launch_ndt_pack_hash(h->stream, c->ndt_hash_keys, c->ndt_hash_vals, c->ndt_hash_kv, cap);
+  VoxelTable& t = c->ndt;
+  HGS_TRY(build_voxel_table(
+      h, c, t, cap, max_cells, true, [&] { launch_ndt_grid_params(h->stream, c->desc, inv_leaf); },
+      [&](unsigned long long* keys, unsigned* vals) { launch_ndt_cell_keys(h->stream, c->desc, inv_leaf, keys, vals); },
+      [&](unsigned long long* keys, unsigned* vals) { launch_ndt_build_cells(h->stream, c->desc, keys, vals, min_pts, t.hash_keys, t.hash_vals, cap - 1, t.cells); }));
+  launch_ndt_pack_hash(h->stream, t.hash_keys, t.hash_vals, t.hash_kv, cap);
   HGS_HIP(h, hipGetLastError());
   c->has_ndt = true;
   c->ndt_resolution = res;
@@ -802,46 +628,13 @@ int ensure_vgicp_target(hgs_handle* h, hgs_cloud* c) {
   const int k = h->prm.correspondence_randomness;
   if (c->has_vg && c->vg_resolution == res && c->vg_cov_k == cov_cache_key(h, k)) return HGS_OK;
   StageTimer tm(h, HGS_STAGE_VOXELIZE);
-  const size_t n = c->n_input;
-  const int max_cells = (int)n + 1;
+  const int max_cells = (int)c->n_input + 1;
   const int cap = next_pow2(std::max<int>(64, 2 * max_cells));
-  if (!c->vg_block || c->vg_hash_cap != cap) {
-    if (c->vg_block) (void)hipFree(c->vg_block);
-    c->vg_block = nullptr;
-    const size_t o_keys = 0, o_vals = align_up((size_t)cap * 4, 256), o_cells = o_vals + align_up((size_t)cap * 4, 256);
-    const size_t bytes = o_cells + (size_t)max_cells * sizeof(NdtCellRec);
-    HGS_HIP(h, hipMalloc(&c->vg_block, bytes));
-    c->vg_block_bytes = bytes;
-    c->vg_hash_keys = (int*)((char*)c->vg_block + o_keys);
-    c->vg_hash_vals = (int*)((char*)c->vg_block + o_vals);
-    c->vg_cells = (NdtCellRec*)((char*)c->vg_block + o_cells);
-    c->vg_hash_cap = cap;
-  }
-  HGS_HIP(h, hipMemsetAsync(c->vg_hash_keys, 0xff, (size_t)cap * 4, h->stream));
-  launch_vgicp_grid_params(h->stream, c->desc, res);
-  if (n > 0) {
-    for (int i = 0; i < 2; i++) {
-      HGS_HIP(h, h->sort_keys[i].reserve(n * sizeof(uint64_t)));
-      HGS_HIP(h, h->sort_vals[i].reserve(n * sizeof(uint32_t)));
-    }
-    launch_vgicp_cell_keys(h->stream, c->desc, res, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>());
-    size_t tmp_bytes = 0;
-    int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                    h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs (size query) failed";
-      return HGS_ERR_HIP;
-    }
-    HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-    rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs failed";
-      return HGS_ERR_HIP;
-    }
-    launch_vgicp_build_cells(h->stream, c->desc, h->sort_keys[1].as<unsigned long long>(), h->sort_vals[1].as<unsigned>(), c->vg_hash_keys,
-                             c->vg_hash_vals, cap - 1, c->vg_cells);
-  }
+  VoxelTable& t = c->vg;
+  HGS_TRY(build_voxel_table(
+      h, c, t, cap, max_cells, false, [&] { launch_vgicp_grid_params(h->stream, c->desc, res); },
+      [&](unsigned long long* keys, unsigned* vals) { launch_vgicp_cell_keys(h->stream, c->desc, res, keys, vals); },
+      [&](unsigned long long* keys, unsigned* vals) { launch_vgicp_build_cells(h->stream, c->desc, keys, vals, t.hash_keys, t.hash_vals, cap - 1, t.cells); }));
   HGS_HIP(h, hipGetLastError());
   c->has_vg = true;
   c->vg_resolution = res;
@@ -849,32 +642,20 @@ int ensure_vgicp_target(hgs_handle* h, hgs_cloud* c) {
   return HGS_OK;
 }
 
-NdtTargetView ndt_target_view(const hgs_handle* h, const hgs_cloud* t) {
+// inv_leaf: 1 / resolution for NDT's tables, 0 for VGICP's (its kernels take the resolution from VgicpConsts)
+NdtTargetView voxel_target_view(const hgs_cloud* c, const VoxelTable& t, float inv_leaf) {
   NdtTargetView tv;
-  tv.hash_keys = t->ndt_hash_keys, tv.hash_vals = t->ndt_hash_vals, tv.cells = t->ndt_cells, tv.meta = t->desc.meta, tv.hash_kv = t->ndt_hash_kv;
-  tv.hash_mask = t->ndt_hash_cap - 1, tv.inv_leaf = 1.0f / (float)h->prm.resolution;
+  tv.hash_keys = t.hash_keys, tv.hash_vals = t.hash_vals, tv.cells = t.cells, tv.meta = c->desc.meta, tv.hash_kv = t.hash_kv;
+  tv.hash_mask = t.hash_cap - 1, tv.inv_leaf = inv_leaf;
   return tv;
 }
-
-NdtTargetView vgicp_target_view(const hgs_cloud* t) {
-  NdtTargetView tv;
-  tv.hash_keys = t->vg_hash_keys, tv.hash_vals = t->vg_hash_vals, tv.cells = t->vg_cells, tv.meta = t->desc.meta, tv.hash_kv = nullptr;
-  tv.hash_mask = t->vg_hash_cap - 1, tv.inv_leaf = 0.f;
-  return tv;
-}
-
-VgicpConsts vgicp_consts(const hgs_params& p) {
-  VgicpConsts c;
-  c.resolution = p.resolution;
-  c.search = p.neighbor_search == HGS_DIRECT27 ? 3 : (p.neighbor_search == HGS_DIRECT7 ? 2 : 1);
-  c.pad = 0;
-  return c;
-}
+NdtTargetView ndt_target_view(const hgs_handle* h, const hgs_cloud* t) { return voxel_target_view(t, t->ndt, 1.0f / (float)h->prm.resolution); }
+NdtTargetView vgicp_target_view(const hgs_cloud* t) { return voxel_target_view(t, t->vg, 0.f); }
 
 TargetView target_view(const hgs_cloud* c) {
   TargetView t;
   t.nodes = c->desc.nodes, t.pts = c->desc.pts, t.lpts = c->desc.lpts, t.cov = c->desc.cov, t.meta = c->desc.meta, t.P = c->P;
-  t.seed_bits = c->has_seed ? c->seed_bits : 0, t.seed_tab = c->has_seed ? static_cast<const unsigned*>(c->seed_block) : nullptr;
+  t.seed_bits = c->has_seed ? c->seed_bits : 0, t.seed_tab = c->has_seed ? c->seed_block.as<const unsigned>() : nullptr;
   return t;
 }
 
@@ -884,62 +665,21 @@ int ensure_seed_grid(hgs_handle* h, hgs_cloud* c) {
   int bits = 12;
   while (bits < 24 && ((size_t)1 << bits) < 4 * c->n_input) bits++;
   const size_t bytes = seed_grid_entries(bits) * sizeof(unsigned);
-  if (!c->seed_block || c->seed_bits != bits) {
-    if (c->seed_block) (void)hipFree(c->seed_block);
-    c->seed_block = nullptr;
-    HGS_HIP(h, hipMalloc(&c->seed_block, bytes));
-    c->seed_block_bytes = bytes, c->seed_bits = bits;
+  if (!c->seed_block.p || c->seed_bits != bits) {
+    HGS_HIP(h, c->seed_block.alloc(bytes));
+    c->seed_bits = bits;
   }
-  HGS_HIP(h, hipMemsetAsync(c->seed_block, 0xff, bytes, h->stream));
-  launch_seed_grid_build(h->stream, c->desc.pts, c->desc.meta, (int)c->n_input, static_cast<unsigned*>(c->seed_block), bits);
+  HGS_HIP(h, hipMemsetAsync(c->seed_block.p, 0xff, bytes, h->stream));
+  launch_seed_grid_build(h->stream, c->desc.pts, c->desc.meta, (int)c->n_input, c->seed_block.as<unsigned>(), bits);
   HGS_HIP(h, hipGetLastError());
   c->has_seed = true;
   return HGS_OK;
 }
 
-GicpConsts gicp_consts(const hgs_params& p) {
-  GicpConsts c;
-  const double thr = p.max_correspondence_distance;
-  c.max_corr2 = thr * thr;
-  c.search_bound2 = c.max_corr2 >= (double)FLT_MAX ? FLT_MAX : nextafterf((float)c.max_corr2, FLT_MAX);
-  c.rotation_eps = p.rotation_epsilon;
-  c.translation_eps = p.transformation_epsilon;
-  c.lm_init_lambda_factor = p.lm_init_lambda_factor;
-  c.lm_max_iterations = p.lm_max_iterations;
-  c.max_iterations = p.max_iterations;
-  c.k_correspondences = p.correspondence_randomness;
-  return c;
-}
-
-// pcl::IterativeClosestPoint as registrations.cpp:57-64 configures it, with DefaultConvergenceCriteria's thresholds (hgs_icp.h)
-IcpConsts icp_consts(const hgs_params& p) {
-  IcpConsts c;
-  const double thr = p.max_correspondence_distance;
-  c.max_corr2 = thr * thr;
-  c.search_bound2 = c.max_corr2 >= (double)FLT_MAX ? FLT_MAX : nextafterf((float)c.max_corr2, FLT_MAX);
-  c.max_iterations = p.max_iterations;
-  c.trans_eps = p.transformation_epsilon;
-  c.rot_thr = p.rotation_epsilon > 0 ? p.rotation_epsilon : 1.0 - p.transformation_epsilon;
-  c.reciprocal = p.icp_reciprocal ? 1 : 0;
-  c.pad = 0;
-  return c;
-}
-
-NdtConsts ndt_consts(const hgs_params& p) {
-  NdtConsts c;
-  const double c1 = 10.0 * (1 - p.ndt_outlier_ratio);
-  const double c2 = p.ndt_outlier_ratio / std::pow(p.resolution, 3);
-  const double d3 = -std::log(c2);
-  c.gauss_d1 = -std::log(c1 + c2) - d3;
-  c.gauss_d2 = -2 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / c.gauss_d1);
-  c.step_size = p.ndt_step_size;
-  c.trans_eps = p.transformation_epsilon;
-  c.max_iterations = p.max_iterations;
-  c.search = p.neighbor_search == HGS_DIRECT1 ? 1 : (p.neighbor_search == HGS_KDTREE ? 0 : 2);
-  c.kdtree_radius2 = (float)(p.resolution * p.resolution);
-  c.line_search = p.ndt_line_search ? 1 : 0;
-  c.upstream_hd1_sign = p.ndt_upstream_hd1_sign;
-  c.pad = std::getenv("HGS_TRACE") ? 1 : 0;  // device-side per-iteration trace (parity debugging)
+// (HGS_TRACE: device-side per-iteration trace, parity debugging; the mapping itself is hgs_consts.h)
+NdtConsts engine_ndt_consts(const hgs_params& p) {
+  NdtConsts c = ndt_consts(p);
+  c.pad = std::getenv("HGS_TRACE") ? 1 : 0;
   return c;
 }
 
@@ -1103,14 +843,250 @@ void drive_lanes(std::vector<BatchLane>& lanes, long max_rounds, F&& enqueue_rou
   }
 }
 
-// getFitnessScore of one lane's problems at the poses stored in h->results (exact 1-NN of every transformed source point
-// in the target; FAST_GICP and ICP seed the search with the final correspondences).
+// What the launches of a batch are sized by, computed once per batch (batch_shape).
+struct BatchShape {
+  int B, max_n;
+  int qpw, nn_tile;                   // queries per packet and points per block of the 1-NN kernels (k_gicp_linearize / k_fitness)
+  bool gicp_round2;                   // the LM round in two launches
+  int lin_qpw, lin_tile, lin_blocks;  // ... whose k_gicp_linearize<true> may run shorter packets
+  int max_blocks, err_blocks;         // rows of the partial-sum buffers / blocks of the 256-point kernels, per problem
+  const CloudDesc* d_descs;           // the sources' descriptors on the device
+};
+
+// lm_rounds: the batch iterates (run_batch); false: a fitness pass alone (run_fitness), which has no two-launch rounds to size for
+int batch_shape(hgs_handle* h, const std::vector<hgs_cloud*>& sources, bool lm_rounds, BatchShape* out) {
+  BatchShape& s = *out;
+  s.B = (int)sources.size();
+  s.max_n = 0;
+  for (hgs_cloud* c : sources) s.max_n = std::max(s.max_n, (int)c->n_input);
+  const int B = s.B, max_n = s.max_n;
+  s.qpw = 64;  // queries per packet of the 1-NN kernels; shorter packets cost a batch ~13 % more work (round 2) ...
+  s.nn_tile = (kBlock / 64) * s.qpw * kNW;                 // points per block of k_gicp_linearize / k_fitness (their own tiling formula)
+  // ... but a launch of a FEW blocks lasts as long as one packet walk, and a shorter packet walks fewer nodes: the two-launch LM rounds of a small single
+  // registration run k_gicp_linearize<true> with 16- / 32-query packets, whose last wave per block redoes the 64-point wave rows so that no bit of the
+  // result depends on the packet size (hgs_kernels.hip).  Same-box (profiles/r06_ab12_nn_qpw.log, r06_ab13): the 13.5 k-point odometry source hgs_align
+  // 0.344 -> 0.315 ms with 16; by size (profiles/r06_nn_qpw_sizes.log): 7 k points -6 %, 11 k -4 %, 16 k -3 %, 22 k -1 %, 64 k +2 % (32 never wins).
+  // nn_qpw (option): 0 = by launch size, 16 / 32 / 64 = that packet.
+  // A launch of a few problems (a single registration: the odometry step, config 2) is a chain of ~4 us kernels in which the two per-problem control launches
+  // of an LM round cost as much as its two point kernels: such launches run the round in TWO launches, the control steps replicated in every block of
+  // k_gicp_linearize<true> / k_gicp_error<true> (hgs_kernels.hip).  The states then alternate between two buffers; a whole round leaves them in the first.
+  s.gicp_round2 = lm_rounds && h->prm.method == HGS_FAST_GICP && h->fused_rounds && max_n <= h->fused_rounds_below &&
+                  (B <= h->fused_rounds_max_problems || (long)B * ((max_n + kBlock - 1) / kBlock) <= (long)h->fused_rounds_max_blocks);
+  const long tiles64 = (long)B * ((max_n + s.nn_tile - 1) / s.nn_tile);
+  s.lin_qpw = !s.gicp_round2 ? 64 : h->nn_qpw > 0 ? h->nn_qpw : tiles64 <= (long)h->nn_qpw16_below ? 16 : tiles64 <= (long)h->nn_qpw32_below ? 32 : 64;
+  s.lin_tile = (kBlock / 64) * s.lin_qpw * kNW;
+  s.lin_blocks = std::max(1, (max_n + s.lin_tile - 1) / s.lin_tile);
+  s.max_blocks = std::max(1, s.lin_qpw < 64 ? (max_n + 63) / 64 : (max_n + s.nn_tile - 1) / s.nn_tile);  // >= the tile (row) count of every kernel of the loop
+  s.err_blocks = std::max(1, (max_n + kBlock - 1) / kBlock);
+  return upload_descs(h, sources, false, &s.d_descs, nullptr);
+}
+
+// getFitnessScore of one lane's problems at the poses stored in h->results (exact 1-NN of every transformed source point in the target).
+// corr_seeds: the sources' corr[] hold their correspondences against THIS target and seed the search; otherwise the target's seed grid does.
 bool corr_seeds_fitness(int method) { return method == HGS_FAST_GICP || method == HGS_ICP; }
-void lane_fitness(hgs_handle* h, BatchLane& L, const CloudDesc* d_descs, double max_range, int max_blocks, int qpw, int nn_tile) {
+void lane_fitness(hgs_handle* h, BatchLane& L, const BatchShape& s, double max_range, bool corr_seeds) {
   StageTimer tm(h, HGS_STAGE_FITNESS);
   DevResult* res = h->results.as<DevResult>() + L.b0;
-  launch_fitness(L.stream, d_descs + L.b0, target_view(h->target), res, max_range, L.partials_err, max_blocks, L.B, corr_seeds_fitness(h->prm.method) ? 1 : 0, qpw);
-  launch_fitness_final(L.stream, d_descs + L.b0, L.partials_err, max_blocks, res, L.B, nn_tile);
+  launch_fitness(L.stream, s.d_descs + L.b0, target_view(h->target), res, max_range, L.partials_err, s.max_blocks, L.B, corr_seeds ? 1 : 0, s.qpw);
+  launch_fitness_final(L.stream, s.d_descs + L.b0, L.partials_err, s.max_blocks, res, L.B, s.nn_tile);
+}
+// behind a lane's result kernel: the fitness pass of a batch that asked for one (FAST_GICP and ICP start it from the final correspondences)
+void lane_fitness_tail(hgs_handle* h, BatchLane& L, const BatchShape& s, const double* fit_max_range) {
+  if (fit_max_range) lane_fitness(h, L, s, *fit_max_range, corr_seeds_fitness(h->prm.method));
+}
+
+// The rounds of a FAST_GICP / FAST_VGICP batch.  guess_in_args: a single GICP registration, whose guess rides in k_gicp_init1's arguments.
+int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_host, bool guess_in_args, const double* fit_max_range) {
+  const int B = s.B, max_blocks = s.max_blocks;
+  hgs_cloud* tgt = h->target;
+  const bool voxel = h->prm.method == HGS_FAST_VGICP;
+  const GicpConsts c = gicp_consts(h->prm);
+  const VgicpConsts vc = vgicp_consts(h->prm);
+  const bool round2 = s.gicp_round2;
+  // One registration without a fitness pass behind it (hgs_align: the odometry step): the kernel that finds it finished writes the result record into
+  // host-mapped memory in front of the mirror's `done` flag; the poll below returns with it — no result kernel, no copy, no synchronisation.
+  const bool early = round2 && B == 1 && !fit_max_range && h->early_result && !h->profiling;
+  DevResult* early_out = nullptr;
+  if (early) {
+    HGS_HIP(h, h->h_early.reserve(sizeof(DevResult)));
+    early_out = h->h_early.as<DevResult>();
+  }
+  HGS_HIP(h, h->states.reserve((size_t)B * sizeof(GicpState) * (round2 ? 2 : 1)));
+  GicpState* st = h->states.as<GicpState>();
+  GicpState* st_other = st + B;
+  const TargetView tv = target_view(tgt);
+  const NdtTargetView vtv = voxel ? vgicp_target_view(tgt) : NdtTargetView{};
+  const long max_rounds = (long)std::max(1, c.max_iterations) * std::max(1, c.lm_max_iterations) + 2 + (round2 ? 1 : 0);  // (round2: a round's accept / reject runs in the next round's first kernel)
+  std::vector<BatchLane> lanes;
+  HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccNdt * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
+  auto finish_lane = [&](BatchLane& L) {
+    if (early && *L.prog.host_done) {  // (not when the lane ran out of rounds: then the result kernel + copy below fetch whatever state it is in)
+      h->early_valid = true;
+      return;
+    }
+    launch_gicp_results(L.stream, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
+    lane_fitness_tail(h, L, s, fit_max_range);
+  };
+  if (guess_in_args) launch_gicp_init1(lanes[0].stream, st, guesses_host, lanes[0].prog);
+  else
+    for (BatchLane& L : lanes) launch_gicp_init(L.stream, st + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, L.B, L.prog);
+  drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
+    const CloudDesc* dd = s.d_descs + L.b0;
+    GicpState* ls = st + L.b0;
+    if (round2) {
+      {
+        StageTimer tm(h, HGS_STAGE_LINEARIZE);
+        launch_gicp_linearize_round2(L.stream, dd, tv, ls, st_other + L.b0, c, L.partials, L.partials_err, max_blocks, s.lin_blocks, L.B, s.lin_qpw, L.prog,
+                                     h->results.as<DevResult>() + L.b0, early_out);
+      }
+      StageTimer tm(h, HGS_STAGE_ERROR);
+      launch_gicp_error_round2(L.stream, dd, tv, st_other + L.b0, ls, c, L.partials, L.partials_err, max_blocks, s.err_blocks, L.B, s.lin_tile);
+      return;
+    }
+    {
+      StageTimer tm(h, HGS_STAGE_LINEARIZE);
+      if (voxel) launch_vgicp_linearize(L.stream, dd, vtv, ls, vc, L.partials, max_blocks, L.B);
+      else launch_gicp_linearize(L.stream, dd, tv, ls, c, L.partials, max_blocks, L.B, s.qpw);
+    }
+    {
+      StageTimer tm(h, HGS_STAGE_SOLVE);
+      launch_gicp_solve(L.stream, dd, ls, c, L.partials, max_blocks, L.B, voxel ? kBlock : s.nn_tile);
+    }
+    {
+      StageTimer tm(h, HGS_STAGE_ERROR);
+      if (voxel) launch_vgicp_error(L.stream, dd, vtv, ls, vc, L.partials_err, max_blocks, L.B);
+      else launch_gicp_error(L.stream, dd, tv, ls, L.partials_err, max_blocks, L.B);
+    }
+    {
+      StageTimer tm(h, HGS_STAGE_SOLVE);
+      launch_gicp_decide(L.stream, dd, ls, c, L.partials_err, max_blocks, L.B, L.prog);
+    }
+  }, finish_lane, early ? (long)h->early_run_ahead : kRunAhead);
+  HGS_TRY(close_lanes(h, lanes));
+  if (h->early_valid) {  // rounds may still be queued (the host runs ahead): the next batch's mirror reset waits for them (make_progress)
+    if (!h->early_event) HGS_HIP(h, hipEventCreateWithFlags(&h->early_event, hipEventDisableTiming));
+    HGS_HIP(h, hipEventRecord(h->early_event, h->stream));
+    h->early_pending = true;
+  }
+  return HGS_OK;
+}
+
+// The rounds of an ICP batch: one correspondence pass + one control step per round; a registration takes at most max(1, max_iterations) rounds
+// (+2 as the other methods)
+int run_icp_rounds(hgs_handle* h, const BatchShape& s, const double* fit_max_range) {
+  const int B = s.B, max_blocks = s.max_blocks;
+  const IcpConsts c = icp_consts(h->prm);
+  HGS_HIP(h, h->states.reserve((size_t)B * sizeof(IcpState)));
+  IcpState* st = h->states.as<IcpState>();
+  const TargetView tv = target_view(h->target);
+  const long max_rounds = (long)std::max(0, c.max_iterations) + 2;
+  std::vector<BatchLane> lanes;
+  HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccIcp * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
+  auto finish_lane = [&](BatchLane& L) {
+    launch_icp_results(L.stream, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
+    lane_fitness_tail(h, L, s, fit_max_range);
+  };
+  for (BatchLane& L : lanes) launch_icp_init(L.stream, st + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, L.B, L.prog);
+  drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
+    {
+      StageTimer tm(h, HGS_STAGE_LINEARIZE);
+      launch_icp_correspond(L.stream, s.d_descs + L.b0, tv, st + L.b0, c, L.partials, max_blocks, L.B);
+    }
+    StageTimer tm(h, HGS_STAGE_SOLVE);
+    launch_icp_solve(L.stream, s.d_descs + L.b0, st + L.b0, c, L.partials, max_blocks, L.B, L.prog);
+  }, finish_lane);
+  return close_lanes(h, lanes);
+}
+
+// Work plan of every lane of an NDT batch: the (problem, tile) items of a pass are numbered by the prefix sums of the problems' tile counts
+// (from n_input: an upper bound of the finite points), and pulled from a queue head in HBM (k_ndt_pass)
+struct NdtLanePlan {
+  int* tile_base;
+  unsigned long long* queues;  // two heads, used alternately (k_ndt_pass)
+  int blocks, chunk;
+};
+int ndt_lane_plans(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const std::vector<BatchLane>& lanes, std::vector<NdtLanePlan>& plans) {
+  plans.assign(lanes.size(), NdtLanePlan{});
+  const size_t per_lane = align_up(16 + (sources.size() + 1) * sizeof(int), 256);
+  bool tile_overflow = false;
+  constexpr long long kMaxNdtBlocks = 1 << 16, kMaxNdtChunk = 1 << 10;  // far above anything HGS_NDT_RESIDENT / HGS_NDT_CHUNK are used with
+  HGS_HIP(h, h->ndt_plan.reserve(per_lane * lanes.size()));
+  void* staged = nullptr;
+  int plan_slot = 0;
+  HGS_HIP(h, h->up.stage(per_lane * lanes.size(), &staged, &plan_slot));
+  std::memset(staged, 0, per_lane * lanes.size());
+  char* const host = static_cast<char*>(staged);
+  for (size_t li = 0; li < lanes.size(); li++) {
+    const BatchLane& L = lanes[li];
+    int* tb = reinterpret_cast<int*>(host + li * per_lane + 16);
+    tb[0] = 0;
+    // k_ndt_pass does its item arithmetic in 32-bit ints (queue head + blocks * chunk must fit): bound the lane's tile count here
+    long long tiles64 = 0;
+    for (int k = 0; k < L.B; k++) {
+      tiles64 += std::max<long long>(1, ((long long)sources[L.b0 + k]->n_input + kBlock - 1) / kBlock);
+      tile_overflow = tile_overflow || tiles64 > (long long)INT_MAX - (long long)kMaxNdtBlocks * kMaxNdtChunk;
+      tb[k + 1] = tile_overflow ? 0 : (int)tiles64;
+    }
+    NdtLanePlan& P = plans[li];
+    const int total = tb[L.B];
+    if (tile_overflow) continue;
+    P.blocks = std::max(1, std::min(total, h->ndt_resident_blocks > 0 ? std::min(h->ndt_resident_blocks, (int)kMaxNdtBlocks) : (lanes.size() > 1 ? 512 : 768)));
+    // largest queue grab (the kernel sizes each grab by guided self-scheduling, at most this many items).  Fixed grabs
+    // measured on the 16 x 119 k batch with 4 lanes: 1 -> 904, 2 -> 1062, 3 -> 980, 4 -> 936, 8 -> 845 registrations/s
+    P.chunk = h->ndt_chunk > 0 ? std::min(h->ndt_chunk, (int)kMaxNdtChunk) : 8;
+    P.queues = reinterpret_cast<unsigned long long*>((char*)h->ndt_plan.p + li * per_lane);
+    P.tile_base = reinterpret_cast<int*>((char*)h->ndt_plan.p + li * per_lane + 16);
+  }
+  if (tile_overflow) {
+    h->err = "NDT batch too large: the tiles of one lane do not fit 32-bit item arithmetic (more than ~5e11 source points in one call)";
+    return HGS_ERR_INVALID_ARGUMENT;
+  }
+  HGS_HIP(h, hipMemcpyAsync(h->ndt_plan.p, host, per_lane * lanes.size(), hipMemcpyHostToDevice, h->stream));  // (round 4: a synchronous hipMemcpy of a pageable vector)
+  HGS_HIP(h, h->up.commit(plan_slot, h->stream));
+  // open_lanes() released lanes 1.. behind an event recorded BEFORE this copy: order them behind the plan as well, or a lane's first
+  // k_ndt_init / k_ndt_pass could read the previous batch's tile_base / queue heads (round-5 advisor finding; tests/test_hip_parity.py
+  // ::test_ndt_batches_of_different_shape_back_to_back poisons the plan between batches)
+  if (lanes.size() > 1) {
+    HGS_HIP(h, hipEventRecord(h->lane_event[0], h->stream));
+    for (size_t i = 1; i < lanes.size(); i++) HGS_HIP(h, hipStreamWaitEvent(lanes[i].stream, h->lane_event[0], 0));
+  }
+  return HGS_OK;
+}
+
+// The rounds of an NDT_OMP batch: one kernel per round, the Newton step inside it — nothing to stagger
+int run_ndt_rounds(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const BatchShape& s, const double* fit_max_range) {
+  const int B = s.B, max_blocks = s.max_blocks;
+  const NdtConsts c = engine_ndt_consts(h->prm);
+  HGS_HIP(h, h->states.reserve((size_t)B * sizeof(NdtState)));
+  HGS_HIP(h, h->angles.reserve((size_t)B * sizeof(NdtAngles)));
+  NdtState* st = h->states.as<NdtState>();
+  NdtAngles* ang = h->angles.as<NdtAngles>();
+  const NdtTargetView tv = ndt_target_view(h, h->target);
+  // the sums are order-independent (hgs_ndt.h): read the sources in Hilbert order whenever they have a search index
+  // (neighbouring lanes then share cells), in input order otherwise
+  if (h->ndt_sort == 1) HGS_TRY(ensure_index(h, sources));
+  bool sorted = h->ndt_sort != 0;
+  for (hgs_cloud* sc : sources) sorted = sorted && sc->has_index;
+  HGS_HIP(h, h->ndt_accum.reserve((size_t)B * sizeof(NdtAccum)));
+  NdtAccum* accum = h->ndt_accum.as<NdtAccum>();  // zeroed by k_ndt_init (one dispatch less than a memset in front of it)
+  // one derivative pass per iteration as ndt_omp runs; up to 1 + 10 with the More-Thuente search
+  const long max_rounds = ((long)c.max_iterations + 4) * (c.line_search ? 11 : 1);
+  std::vector<BatchLane> lanes;
+  HGS_TRY(open_lanes(h, B, (size_t)max_blocks * 2 * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
+  auto finish_lane = [&](BatchLane& L) {
+    launch_ndt_results(L.stream, s.d_descs + L.b0, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
+    lane_fitness_tail(h, L, s, fit_max_range);
+  };
+  std::vector<NdtLanePlan> plans;
+  HGS_TRY(ndt_lane_plans(h, sources, lanes, plans));
+  for (BatchLane& L : lanes) launch_ndt_init(L.stream, st + L.b0, ang + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, c, L.B, L.prog, accum + L.b0);
+  drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
+    StageTimer tm(h, HGS_STAGE_LINEARIZE);
+    const NdtLanePlan& P = plans[&L - lanes.data()];
+    launch_ndt_pass(L.stream, s.d_descs + L.b0, tv, st + L.b0, ang + L.b0, c, accum + L.b0, P.tile_base, P.queues, L.B, (int)(L.round & 1), P.blocks, P.chunk,
+                    sorted ? 1 : 0, 0, L.prog);
+  }, finish_lane);
+  return close_lanes(h, lanes);
 }
 
 // Run all B registrations (sources vs the handle's target) to completion; results land in h->results (device).
@@ -1121,13 +1097,14 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
   h->early_valid = false;
   hgs_cloud* tgt = h->target;
   const int method = h->prm.method;
+  const bool gicp = method == HGS_FAST_GICP || method == HGS_FAST_VGICP;
   std::vector<hgs_cloud*> all(sources);
   if (fit_max_range) {
     std::vector<hgs_cloud*> searched(sources);
     searched.push_back(tgt);
     HGS_TRY(ensure_index(h, searched));
   }
-  if (method == HGS_FAST_GICP || method == HGS_FAST_VGICP) {
+  if (gicp) {
     all.push_back(tgt);
     HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
     if (method == HGS_FAST_VGICP) HGS_TRY(ensure_vgicp_target(h, tgt));
@@ -1140,215 +1117,17 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
     HGS_TRY(ensure_ndt_target(h, tgt));
   }
   if (fit_max_range && method != HGS_FAST_GICP) HGS_TRY(ensure_seed_grid(h, tgt));  // getFitnessScore without correspondences to start from (k_fitness)
-  int max_n = 0;
-  for (hgs_cloud* c : sources) max_n = std::max(max_n, (int)c->n_input);
-  size_t total_q = 0;
-  for (hgs_cloud* c : sources) total_q += c->n_input;
-  (void)total_q;
-  const int qpw = 64;  // queries per packet of the 1-NN kernels; shorter packets cost a batch ~13 % more work (round 2) ...
-  const int nn_tile = (kBlock / 64) * qpw * kNW;                 // points per block of k_gicp_linearize / k_fitness (their own tiling formula)
-  // ... but a launch of a FEW blocks lasts as long as one packet walk, and a shorter packet walks fewer nodes: the two-launch LM rounds of a small single
-  // registration run k_gicp_linearize<true> with 16- / 32-query packets, whose last wave per block redoes the 64-point wave rows so that no bit of the
-  // result depends on the packet size (hgs_kernels.hip).  Same-box (profiles/r06_ab12_nn_qpw.log, r06_ab13): the 13.5 k-point odometry source hgs_align
-  // 0.344 -> 0.315 ms with 16; by size (profiles/r06_nn_qpw_sizes.log): 7 k points -6 %, 11 k -4 %, 16 k -3 %, 22 k -1 %, 64 k +2 % (32 never wins).
-  // nn_qpw (option): 0 = by launch size, 16 / 32 / 64 = that packet.
-  const bool gicp_round2 = method == HGS_FAST_GICP && h->fused_rounds && max_n <= h->fused_rounds_below &&
-                           (B <= h->fused_rounds_max_problems || (long)B * ((max_n + kBlock - 1) / kBlock) <= (long)h->fused_rounds_max_blocks);
-  const long tiles64 = (long)B * ((max_n + nn_tile - 1) / nn_tile);
-  const int lin_qpw = !gicp_round2 ? 64 : h->nn_qpw > 0 ? h->nn_qpw : tiles64 <= (long)h->nn_qpw16_below ? 16 : tiles64 <= (long)h->nn_qpw32_below ? 32 : 64;
-  const int lin_tile = (kBlock / 64) * lin_qpw * kNW;
-  const int lin_blocks = std::max(1, (max_n + lin_tile - 1) / lin_tile);
-  const int max_blocks = std::max(1, lin_qpw < 64 ? (max_n + 63) / 64 : (max_n + nn_tile - 1) / nn_tile);  // >= the tile (row) count of every kernel of the loop
-  const int err_blocks = std::max(1, (max_n + kBlock - 1) / kBlock);
-  const CloudDesc* d_descs = nullptr;
-  HGS_TRY(upload_descs(h, sources, false, &d_descs, nullptr));
+  BatchShape s;
+  HGS_TRY(batch_shape(h, sources, true, &s));
   const bool guess_in_args = B == 1 && method == HGS_FAST_GICP;  // (a single GICP registration: the guess rides in k_gicp_init1's arguments)
   HGS_HIP(h, h->guesses.reserve((size_t)B * 16 * sizeof(float)));
   if (!guess_in_args) HGS_HIP(h, h->up.upload(h->guesses.p, guesses_host, (size_t)B * 16 * sizeof(float), h->stream));  // (the caller's array is pageable: through a pinned slot)
-  HGS_HIP(h, h->done.reserve(64));
   HGS_HIP(h, h->results.reserve((size_t)B * sizeof(DevResult)));
-  HGS_HIP(h, h->partials.reserve((size_t)B * max_blocks * kAccNdt * sizeof(double)));
-  HGS_HIP(h, h->partials_err.reserve((size_t)B * max_blocks * 2 * sizeof(double)));
-  if (method == HGS_FAST_GICP || method == HGS_FAST_VGICP) {
-    const bool voxel = method == HGS_FAST_VGICP;
-    const GicpConsts c = gicp_consts(h->prm);
-    const VgicpConsts vc = vgicp_consts(h->prm);
-    // A launch of a few problems (a single registration: the odometry step, config 2) is a chain of ~4 us kernels in which the two per-problem control launches
-    // of an LM round cost as much as its two point kernels: such launches run the round in TWO launches, the control steps replicated in every block of
-    // k_gicp_linearize<true> / k_gicp_error<true> (hgs_kernels.hip).  The states then alternate between two buffers; a whole round leaves them in the first.
-    const bool round2 = gicp_round2;
-    // One registration without a fitness pass behind it (hgs_align: the odometry step): the kernel that finds it finished writes the result record into
-    // host-mapped memory in front of the mirror's `done` flag; the poll below returns with it — no result kernel, no copy, no synchronisation.
-    const bool early = round2 && B == 1 && !fit_max_range && h->early_result && !h->profiling;
-    DevResult* early_out = nullptr;
-    if (early) {
-      HGS_HIP(h, h->h_early.reserve(sizeof(DevResult)));
-      early_out = h->h_early.as<DevResult>();
-    }
-    HGS_HIP(h, h->states.reserve((size_t)B * sizeof(GicpState) * (round2 ? 2 : 1)));
-    GicpState* st = h->states.as<GicpState>();
-    GicpState* st_other = st + B;
-    const TargetView tv = target_view(tgt);
-    const NdtTargetView vtv = voxel ? vgicp_target_view(tgt) : NdtTargetView{};
-    const long max_rounds = (long)std::max(1, c.max_iterations) * std::max(1, c.lm_max_iterations) + 2 + (round2 ? 1 : 0);  // (round2: a round's accept / reject runs in the next round's first kernel)
-    std::vector<BatchLane> lanes;
-    HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccNdt * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, err_blocks));
-    auto finish_lane = [&](BatchLane& L) {
-      if (early && *L.prog.host_done) {  // (not when the lane ran out of rounds: then the result kernel + copy below fetch whatever state it is in)
-        h->early_valid = true;
-        return;
-      }
-      launch_gicp_results(L.stream, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
-      if (fit_max_range) lane_fitness(h, L, d_descs, *fit_max_range, max_blocks, qpw, nn_tile);
-    };
-    if (guess_in_args) launch_gicp_init1(lanes[0].stream, st, guesses_host, lanes[0].prog);
-    else
-      for (BatchLane& L : lanes) launch_gicp_init(L.stream, st + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, L.B, L.prog);
-    drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
-      const CloudDesc* dd = d_descs + L.b0;
-      GicpState* ls = st + L.b0;
-      if (round2) {
-        {
-          StageTimer tm(h, HGS_STAGE_LINEARIZE);
-          launch_gicp_linearize_round2(L.stream, dd, tv, ls, st_other + L.b0, c, L.partials, L.partials_err, max_blocks, lin_blocks, L.B, lin_qpw, L.prog,
-                                       h->results.as<DevResult>() + L.b0, early_out);
-        }
-        StageTimer tm(h, HGS_STAGE_ERROR);
-        launch_gicp_error_round2(L.stream, dd, tv, st_other + L.b0, ls, c, L.partials, L.partials_err, max_blocks, err_blocks, L.B, lin_tile);
-        return;
-      }
-      {
-        StageTimer tm(h, HGS_STAGE_LINEARIZE);
-        if (voxel) launch_vgicp_linearize(L.stream, dd, vtv, ls, vc, L.partials, max_blocks, L.B);
-        else launch_gicp_linearize(L.stream, dd, tv, ls, c, L.partials, max_blocks, L.B, qpw);
-      }
-      {
-        StageTimer tm(h, HGS_STAGE_SOLVE);
-        launch_gicp_solve(L.stream, dd, ls, c, L.partials, max_blocks, L.B, voxel ? kBlock : nn_tile);
-      }
-      {
-        StageTimer tm(h, HGS_STAGE_ERROR);
-        if (voxel) launch_vgicp_error(L.stream, dd, vtv, ls, vc, L.partials_err, max_blocks, L.B);
-        else launch_gicp_error(L.stream, dd, tv, ls, L.partials_err, max_blocks, L.B);
-      }
-      {
-        StageTimer tm(h, HGS_STAGE_SOLVE);
-        launch_gicp_decide(L.stream, dd, ls, c, L.partials_err, max_blocks, L.B, L.prog);
-      }
-    }, finish_lane, early ? (long)h->early_run_ahead : kRunAhead);
-    HGS_TRY(close_lanes(h, lanes));
-    if (h->early_valid) {  // rounds may still be queued (the host runs ahead): the next batch's mirror reset waits for them (make_progress)
-      if (!h->early_event) HGS_HIP(h, hipEventCreateWithFlags(&h->early_event, hipEventDisableTiming));
-      HGS_HIP(h, hipEventRecord(h->early_event, h->stream));
-      h->early_pending = true;
-    }
-  } else if (method == HGS_ICP) {
-    // one correspondence pass + one control step per round: a registration takes at most max(1, max_iterations) rounds (+2 as the other methods)
-    const IcpConsts c = icp_consts(h->prm);
-    HGS_HIP(h, h->states.reserve((size_t)B * sizeof(IcpState)));
-    IcpState* st = h->states.as<IcpState>();
-    const TargetView tv = target_view(tgt);
-    const long max_rounds = (long)std::max(0, c.max_iterations) + 2;
-    std::vector<BatchLane> lanes;
-    HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccIcp * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, err_blocks));
-    auto finish_lane = [&](BatchLane& L) {
-      launch_icp_results(L.stream, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
-      if (fit_max_range) lane_fitness(h, L, d_descs, *fit_max_range, max_blocks, qpw, nn_tile);
-    };
-    for (BatchLane& L : lanes) launch_icp_init(L.stream, st + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, L.B, L.prog);
-    drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
-      {
-        StageTimer tm(h, HGS_STAGE_LINEARIZE);
-        launch_icp_correspond(L.stream, d_descs + L.b0, tv, st + L.b0, c, L.partials, max_blocks, L.B);
-      }
-      StageTimer tm(h, HGS_STAGE_SOLVE);
-      launch_icp_solve(L.stream, d_descs + L.b0, st + L.b0, c, L.partials, max_blocks, L.B, L.prog);
-    }, finish_lane);
-    HGS_TRY(close_lanes(h, lanes));
-  } else {
-    const NdtConsts c = ndt_consts(h->prm);
-    HGS_HIP(h, h->states.reserve((size_t)B * sizeof(NdtState)));
-    HGS_HIP(h, h->angles.reserve((size_t)B * sizeof(NdtAngles)));
-    NdtState* st = h->states.as<NdtState>();
-    NdtAngles* ang = h->angles.as<NdtAngles>();
-    const NdtTargetView tv = ndt_target_view(h, tgt);
-    // the sums are order-independent (hgs_ndt.h): read the sources in Hilbert order whenever they have a search index
-    // (neighbouring lanes then share cells), in input order otherwise
-    if (h->ndt_sort == 1) HGS_TRY(ensure_index(h, sources));
-    bool sorted = h->ndt_sort != 0;
-    for (hgs_cloud* sc : sources) sorted = sorted && sc->has_index;
-    HGS_HIP(h, h->ndt_accum.reserve((size_t)B * sizeof(NdtAccum)));
-    NdtAccum* accum = h->ndt_accum.as<NdtAccum>();  // zeroed by k_ndt_init (one dispatch less than a memset in front of it)
-    // work plan of every lane: the (problem, tile) items of a pass are numbered by the prefix sums of the problems' tile counts
-    // (from n_input: an upper bound of the finite points), and pulled from a queue head in HBM (k_ndt_pass)
-    // one derivative pass per iteration as ndt_omp runs; up to 1 + 10 with the More-Thuente search
-    const long max_rounds = ((long)c.max_iterations + 4) * (c.line_search ? 11 : 1);
-    std::vector<BatchLane> lanes;
-    HGS_TRY(open_lanes(h, B, (size_t)max_blocks * 2 * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, err_blocks));
-    auto finish_lane = [&](BatchLane& L) {
-      launch_ndt_results(L.stream, d_descs + L.b0, st + L.b0, h->results.as<DevResult>() + L.b0, L.B);
-      if (fit_max_range) lane_fitness(h, L, d_descs, *fit_max_range, max_blocks, qpw, nn_tile);
-    };
-    struct LanePlan {
-      int* tile_base;
-      unsigned long long* queues;  // two heads, used alternately (k_ndt_pass)
-      int blocks, chunk;
-    };
-    std::vector<LanePlan> plans(lanes.size());
-    {
-      const size_t per_lane = align_up(16 + ((size_t)B + 1) * sizeof(int), 256);
-      bool tile_overflow = false;
-      constexpr long long kMaxNdtBlocks = 1 << 16, kMaxNdtChunk = 1 << 10;  // far above anything HGS_NDT_RESIDENT / HGS_NDT_CHUNK are used with
-      HGS_HIP(h, h->ndt_plan.reserve(per_lane * lanes.size()));
-      void* staged = nullptr;
-      int plan_slot = 0;
-      HGS_HIP(h, h->up.stage(per_lane * lanes.size(), &staged, &plan_slot));
-      std::memset(staged, 0, per_lane * lanes.size());
-      char* const host = static_cast<char*>(staged);
-      for (size_t li = 0; li < lanes.size(); li++) {
-        const BatchLane& L = lanes[li];
-        int* tb = reinterpret_cast<int*>(host + li * per_lane + 16);
-        tb[0] = 0;
-        // k_ndt_pass does its item arithmetic in 32-bit ints (queue head + blocks * chunk must fit): bound the lane's tile count here
-        long long tiles64 = 0;
-        for (int k = 0; k < L.B; k++) {
-          tiles64 += std::max<long long>(1, ((long long)sources[L.b0 + k]->n_input + kBlock - 1) / kBlock);
-          tile_overflow = tile_overflow || tiles64 > (long long)INT_MAX - (long long)kMaxNdtBlocks * kMaxNdtChunk;
-          tb[k + 1] = tile_overflow ? 0 : (int)tiles64;
-        }
-        LanePlan& P = plans[li];
-        const int total = tb[L.B];
-        if (tile_overflow) continue;
-        P.blocks = std::max(1, std::min(total, h->ndt_resident_blocks > 0 ? std::min(h->ndt_resident_blocks, (int)kMaxNdtBlocks) : (lanes.size() > 1 ? 512 : 768)));
-        // largest queue grab (the kernel sizes each grab by guided self-scheduling, at most this many items).  Fixed grabs
-        // measured on the 16 x 119 k batch with 4 lanes: 1 -> 904, 2 -> 1062, 3 -> 980, 4 -> 936, 8 -> 845 registrations/s
-        P.chunk = h->ndt_chunk > 0 ? std::min(h->ndt_chunk, (int)kMaxNdtChunk) : 8;
-        P.queues = reinterpret_cast<unsigned long long*>((char*)h->ndt_plan.p + li * per_lane);
-        P.tile_base = reinterpret_cast<int*>((char*)h->ndt_plan.p + li * per_lane + 16);
-      }
-      if (tile_overflow) {
-        h->err = "NDT batch too large: the tiles of one lane do not fit 32-bit item arithmetic (more than ~5e11 source points in one call)";
-        return HGS_ERR_INVALID_ARGUMENT;
-      }
-      HGS_HIP(h, hipMemcpyAsync(h->ndt_plan.p, host, per_lane * lanes.size(), hipMemcpyHostToDevice, h->stream));  // (round 4: a synchronous hipMemcpy of a pageable vector)
-      HGS_HIP(h, h->up.commit(plan_slot, h->stream));
-      // open_lanes() released lanes 1.. behind an event recorded BEFORE this copy: order them behind the plan as well, or a lane's first
-      // k_ndt_init / k_ndt_pass could read the previous batch's tile_base / queue heads (round-5 advisor finding; tests/test_hip_parity.py
-      // ::test_ndt_batches_of_different_shape_back_to_back poisons the plan between batches)
-      if (lanes.size() > 1) {
-        HGS_HIP(h, hipEventRecord(h->lane_event[0], h->stream));
-        for (size_t i = 1; i < lanes.size(); i++) HGS_HIP(h, hipStreamWaitEvent(lanes[i].stream, h->lane_event[0], 0));
-      }
-    }
-    for (BatchLane& L : lanes) launch_ndt_init(L.stream, st + L.b0, ang + L.b0, h->guesses.as<float>() + (size_t)L.b0 * 16, c, L.B, L.prog, accum + L.b0);
-    drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
-      StageTimer tm(h, HGS_STAGE_LINEARIZE);
-      const LanePlan& P = plans[&L - lanes.data()];
-      launch_ndt_pass(L.stream, d_descs + L.b0, tv, st + L.b0, ang + L.b0, c, accum + L.b0, P.tile_base, P.queues, L.B, (int)(L.round & 1), P.blocks, P.chunk,
-                      sorted ? 1 : 0, 0, L.prog);
-    }, finish_lane);  // (NDT: one kernel per round, the Newton step inside it — nothing to stagger)
-    HGS_TRY(close_lanes(h, lanes));
-  }
+  HGS_HIP(h, h->partials.reserve((size_t)B * s.max_blocks * kAccNdt * sizeof(double)));
+  HGS_HIP(h, h->partials_err.reserve((size_t)B * s.max_blocks * 2 * sizeof(double)));
+  if (gicp) HGS_TRY(run_gicp_rounds(h, s, guesses_host, guess_in_args, fit_max_range));
+  else if (method == HGS_ICP) HGS_TRY(run_icp_rounds(h, s, fit_max_range));
+  else HGS_TRY(run_ndt_rounds(h, sources, s, fit_max_range));
   HGS_HIP(h, hipGetLastError());
   return HGS_OK;
 }
@@ -1357,23 +1136,16 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
 // use_corr_seeds: the sources' corr[] hold their correspondences against THIS target (hgs_fitness right behind a GICP align); otherwise the
 // searches start from the target's seed grid
 int run_fitness(hgs_handle* h, const std::vector<hgs_cloud*>& sources, double max_range, bool use_corr_seeds) {
-  const int B = (int)sources.size();
   std::vector<hgs_cloud*> all(sources);
   all.push_back(h->target);
   HGS_TRY(ensure_index(h, all));
   if (!use_corr_seeds) HGS_TRY(ensure_seed_grid(h, h->target));
-  int max_n = 0;
-  for (hgs_cloud* c : sources) max_n = std::max(max_n, (int)c->n_input);
-  const int qpw = 64;
-  const int nn_tile = (kBlock / 64) * qpw * kNW;
-  const int max_blocks = std::max(1, (max_n + nn_tile - 1) / nn_tile);
-  const CloudDesc* d_descs = nullptr;
-  HGS_TRY(upload_descs(h, sources, false, &d_descs, nullptr));
-  HGS_HIP(h, h->partials_err.reserve((size_t)B * max_blocks * 2 * sizeof(double)));
-  StageTimer tm(h, HGS_STAGE_FITNESS);
-  launch_fitness(h->stream, d_descs, target_view(h->target), h->results.as<DevResult>(), max_range, h->partials_err.as<double>(), max_blocks, B,
-                 use_corr_seeds ? 1 : 0, qpw);
-  launch_fitness_final(h->stream, d_descs, h->partials_err.as<double>(), max_blocks, h->results.as<DevResult>(), B, nn_tile);
+  BatchShape s;
+  HGS_TRY(batch_shape(h, sources, false, &s));
+  HGS_HIP(h, h->partials_err.reserve((size_t)s.B * s.max_blocks * 2 * sizeof(double)));
+  BatchLane whole;  // every problem on the engine's stream
+  whole.stream = h->stream, whole.B = s.B, whole.partials_err = h->partials_err.as<double>();
+  lane_fitness(h, whole, s, max_range, use_corr_seeds);
   HGS_HIP(h, hipGetLastError());
   return HGS_OK;
 }
@@ -1386,6 +1158,9 @@ int fetch_results(hgs_handle* h, int B, std::vector<DevResult>& out) {
   return HGS_OK;
 }
 
+// pcl::Registration::getFitnessScore: the mean squared distance of the inliers, DBL_MAX without any
+double fitness_score(const DevResult& d) { return d.fit_count > 0 ? d.fit_sum / (double)d.fit_count : std::numeric_limits<double>::max(); }
+
 void to_public(const DevResult& d, int candidate, bool with_fitness, hgs_result* r) {
   std::memcpy(r->final_transformation, d.T, sizeof(float) * 16);
   r->converged = d.converged;
@@ -1396,7 +1171,7 @@ void to_public(const DevResult& d, int candidate, bool with_fitness, hgs_result*
   r->reserved = 0;
   if (with_fitness) {
     r->num_inliers = d.fit_count;
-    r->fitness_score = d.fit_count > 0 ? d.fit_sum / (double)d.fit_count : std::numeric_limits<double>::max();
+    r->fitness_score = fitness_score(d);
   } else {
     r->num_inliers = 0;
     r->fitness_score = std::numeric_limits<double>::quiet_NaN();
@@ -1435,7 +1210,45 @@ int status_of_current_exception(hgs_handle* h) noexcept {
   return rc;
 }
 
+// hgs_set_target / hgs_set_source and their _cloud forms: `role` is the engine's target or source, `own` whether the engine frees it
+int set_role_cloud(hgs_handle* h, hgs_cloud* c, hgs_cloud* hgs_handle::*role, bool hgs_handle::*own) {
+  ApiLock lock(h);
+  if (!h || !c || c->owner != h) return HGS_ERR_INVALID_ARGUMENT;  // clouds belong to the engine (stream) that created them
+  if (h->*own && h->*role != c) cloud_free(h->*role);
+  h->*role = c;
+  h->*own = false;
+  return HGS_OK;
+}
+int set_role_points(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, hgs_cloud* hgs_handle::*role, bool hgs_handle::*own) {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  hgs_cloud* c = nullptr;
+  HGS_TRY(hgs_cloud_create(h, pts, n, stride_bytes, &c));
+  if (h->*own) cloud_free(h->*role);  // (its block is reused in stream order, or freed by hipFree, which waits by itself)
+  h->*role = c;
+  h->*own = true;
+  return HGS_OK;
+}
+
 }  // namespace
+
+// Everything the engine holds goes here, and only here (hgs_destroy, and hgs_create when it fails half way).  The buffers, rings and pooled blocks free
+// themselves once this body is through (hgs_resources.h); what it spells out is the order that matters.
+hgs_handle::~hgs_handle() {
+  (void)hipSetDevice(device);  // first: one process may hold engines on several GPUs
+  synchronize_streams();       // nothing below is still being read by a queued kernel or copy
+  pack_pool.shutdown();        // the workers write into pinned memory (up_big, h_xform) that the members' destructors free
+  if (comm) hgs::comm_destroy(comm);
+  for (hipEvent_t ev : lane_event)
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {comm_event, early_event, up_big_event})
+    if (ev) (void)hipEventDestroy(ev);
+  for (const std::vector<ProfEvent>* list : {&prof_events, &prof_free})
+    for (const ProfEvent& ev : *list) (void)hipEventDestroy(ev.a), (void)hipEventDestroy(ev.b);
+  for (hipStream_t ls : lane_stream)
+    if (ls) (void)hipStreamDestroy(ls), streams_in_use(device).fetch_sub(1, std::memory_order_relaxed);  // (counted where each was created: open_lanes,
+  if (stream) (void)hipStreamDestroy(stream), streams_in_use(device).fetch_sub(1, std::memory_order_relaxed);  //  hgs_create)
+}
 
 // =================================================================================================== C ABI
 extern "C" {
@@ -1446,8 +1259,7 @@ int hgs_abi_version(void) { return HGS_ABI_VERSION; }
 // should not — the library now reads GPU_MAX_HW_QUEUES (HIP's own variable), HGS_COMM_TIMEOUT_MS and HGS_TRACE only.  The Python harness maps
 // HGS_ENGINE_OPTIONS="key=value,..." onto this call (hdl_graph_slam_amd/registration.py); nothing in adapters/ uses it.
 int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !key) return HGS_ERR_INVALID_ARGUMENT;
   const std::string k(key);
   if (k == "batch_lanes") h->batch_lanes = value <= 0 ? 0 : std::min(kMaxLanes, value);                  // 0: open_lanes chooses
@@ -1547,10 +1359,7 @@ int hgs_destroy(hgs_handle* h) try {
   // hgs_destroy must not be called concurrently with other calls on the engine or its clouds (include/hgs_registration.h)
   { std::lock_guard<std::recursive_mutex> wait_for_running_call(h->api_mutex); }
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (hipStream_t ls : h->lane_stream)
-    if (ls) (void)hipStreamSynchronize(ls);
-  if (h->comm) hgs::comm_destroy(h->comm), h->comm = nullptr;
+  h->synchronize_streams();
   if (h->own_target) cloud_free(h->target);
   if (h->own_source) cloud_free(h->source);
   // clouds the caller still holds (hgs_cloud_create / hgs_prefilter results, cached keyframes): their device memory goes with
@@ -1560,35 +1369,6 @@ int hgs_destroy(hgs_handle* h) try {
     c->owner = nullptr;
     c->n_input = 0;
   }
-  h->live_clouds.clear();
-  DeviceBuffer* bufs[] = {&h->staging, &h->sort_keys[0], &h->sort_keys[1], &h->sort_vals[0], &h->sort_vals[1], &h->sort_tmp, &h->descs, &h->states,
-                          &h->angles,  &h->partials,     &h->partials_err, &h->results,      &h->guesses,      &h->done,     &h->misc,
-                          &h->pf_a,    &h->pf_b,         &h->pf_keep,      &h->pf_slot,      &h->pf_small,     &h->pf_dist,      &h->ndt_accum,    &h->ndt_plan,     &h->cov_raw,      &h->pf_ukeys,
-                          &h->comm_send, &h->comm_recv,    &h->comm_ids};
-  for (DeviceBuffer* b : bufs) b->release();
-  for (int i = 0; i < kMaxLanes - 1; i++) h->lane_partials[i].release(), h->lane_partials_err[i].release();
-  for (hipEvent_t ev : h->lane_event)
-    if (ev) (void)hipEventDestroy(ev);
-  if (h->comm_event) (void)hipEventDestroy(h->comm_event);
-  if (h->early_event) (void)hipEventDestroy(h->early_event);
-  for (hipStream_t ls : h->lane_stream)
-    if (ls) (void)hipStreamDestroy(ls), streams_in_use(h->device).fetch_sub(1, std::memory_order_relaxed);
-  for (auto& blk : h->block_pool) (void)hipFree(blk.first);
-  h->block_pool.clear();
-  h->up.release();
-  h->up_points.release();
-  h->pack_pool.shutdown();
-  h->up_big.release();
-  if (h->up_big_event) (void)hipEventDestroy(h->up_big_event);
-  h->h_results.release();
-  h->h_small.release();
-  h->h_comm.release();
-  h->h_flags.release();
-  h->h_early.release();
-  h->h_xform.release();
-  for (auto& ev : h->prof_events) (void)hipEventDestroy(ev.a), (void)hipEventDestroy(ev.b);
-  for (auto& ev : h->prof_free) (void)hipEventDestroy(ev.a), (void)hipEventDestroy(ev.b);
-  if (h->stream) (void)hipStreamDestroy(h->stream), streams_in_use(h->device).fetch_sub(1, std::memory_order_relaxed);
   delete h;
   return HGS_OK;
 } catch (...) {
@@ -1598,8 +1378,7 @@ int hgs_destroy(hgs_handle* h) try {
 const char* hgs_last_error(const hgs_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int hgs_cloud_create(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, hgs_cloud** out) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !out || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes % 4) != 0 || n > (size_t)1 << 30) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   const bool trace = h->upload_trace != 0;  // host-side phase times of an upload on stderr (diagnostics: hgs_debug_set_option "upload_trace")
@@ -1643,8 +1422,7 @@ int hgs_cloud_create(hgs_handle* h, const void* pts, size_t n, size_t stride_byt
 }
 
 int hgs_cloud_destroy(hgs_cloud* c) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (c && c->owner) api_lock__ = std::unique_lock<std::recursive_mutex>(c->owner->api_mutex);
+  ApiLock lock(c);
   if (!c) return HGS_OK;
   hgs_handle* h = c->owner;
   if (h) {
@@ -1664,12 +1442,11 @@ size_t hgs_cloud_size(const hgs_cloud* c) { return c ? c->n_input : 0; }
 
 size_t hgs_cloud_device_bytes(const hgs_cloud* c) {
   if (!c || !c->owner) return 0;
-  return (c->block ? c->block_bytes : 0) + (c->ndt_block ? c->ndt_block_bytes : 0) + (c->vg_block ? c->vg_block_bytes : 0) + (c->seed_block ? c->seed_block_bytes : 0);
+  return c->block.cap + c->ndt.block.cap + c->vg.block.cap + c->seed_block.cap;
 }
 
 int hgs_cloud_invalidate(hgs_cloud* c) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (c && c->owner) api_lock__ = std::unique_lock<std::recursive_mutex>(c->owner->api_mutex);
+  ApiLock lock(c);
   if (!c) return HGS_ERR_INVALID_ARGUMENT;
   c->has_index = false, c->has_cov = false, c->has_ndt = false, c->has_vg = false, c->has_seed = false;
   // also forget the correspondences of earlier registrations (they seed the next search): a truly cold cloud.  No launch here — 65
@@ -1682,57 +1459,28 @@ int hgs_cloud_invalidate(hgs_cloud* c) try {
 }
 
 int hgs_set_target_cloud(hgs_handle* h, hgs_cloud* c) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
-  if (!h || !c || c->owner != h) return HGS_ERR_INVALID_ARGUMENT;  // clouds belong to the engine (stream) that created them
-  if (h->own_target && h->target != c) cloud_free(h->target);
-  h->target = c;
-  h->own_target = false;
-  return HGS_OK;
+  return set_role_cloud(h, c, &hgs_handle::target, &hgs_handle::own_target);
 } catch (...) {
   return status_of_current_exception(h);
 }
 int hgs_set_source_cloud(hgs_handle* h, hgs_cloud* c) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
-  if (!h || !c || c->owner != h) return HGS_ERR_INVALID_ARGUMENT;
-  if (h->own_source && h->source != c) cloud_free(h->source);
-  h->source = c;
-  h->own_source = false;
-  return HGS_OK;
+  return set_role_cloud(h, c, &hgs_handle::source, &hgs_handle::own_source);
 } catch (...) {
   return status_of_current_exception(h);
 }
 int hgs_set_target(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
-  if (!h) return HGS_ERR_INVALID_ARGUMENT;
-  hgs_cloud* c = nullptr;
-  HGS_TRY(hgs_cloud_create(h, pts, n, stride_bytes, &c));
-  if (h->own_target) cloud_free(h->target);
-  h->target = c;
-  h->own_target = true;
-  return HGS_OK;
+  return set_role_points(h, pts, n, stride_bytes, &hgs_handle::target, &hgs_handle::own_target);
 } catch (...) {
   return status_of_current_exception(h);
 }
 int hgs_set_source(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
-  if (!h) return HGS_ERR_INVALID_ARGUMENT;
-  hgs_cloud* c = nullptr;
-  HGS_TRY(hgs_cloud_create(h, pts, n, stride_bytes, &c));
-  if (h->own_source) cloud_free(h->source);  // (its block is reused in stream order, or freed by hipFree, which waits by itself)
-  h->source = c;
-  h->own_source = true;
-  return HGS_OK;
+  return set_role_points(h, pts, n, stride_bytes, &hgs_handle::source, &hgs_handle::own_source);
 } catch (...) {
   return status_of_current_exception(h);
 }
 
 int hgs_align(hgs_handle* h, const float guess[16], hgs_result* out) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !guess || !out) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->target) return HGS_ERR_NO_TARGET;
   if (!h->source) return HGS_ERR_NO_SOURCE;
@@ -1751,8 +1499,7 @@ int hgs_align(hgs_handle* h, const float guess[16], hgs_result* out) try {
 }
 
 int hgs_transform_source(hgs_handle* h, const float T[16], void* out_pts, size_t stride_bytes) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !T || !out_pts || stride_bytes < 12) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->source) return HGS_ERR_NO_SOURCE;
   HGS_TRY(set_device(h));
@@ -1793,8 +1540,7 @@ int hgs_transform_source(hgs_handle* h, const float T[16], void* out_pts, size_t
 }
 
 int hgs_fitness(hgs_handle* h, const float T[16], double max_range, double* score, uint32_t* num_inliers) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !T || !score) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->target) return HGS_ERR_NO_TARGET;
   if (!h->source) return HGS_ERR_NO_SOURCE;
@@ -1804,7 +1550,7 @@ int hgs_fitness(hgs_handle* h, const float T[16], double max_range, double* scor
   HGS_TRY(run_fitness(h, src, max_range, corr_seeds_fitness(h->prm.method)));
   std::vector<DevResult> r;
   HGS_TRY(fetch_results(h, 1, r));
-  *score = r[0].fit_count > 0 ? r[0].fit_sum / (double)r[0].fit_count : std::numeric_limits<double>::max();
+  *score = fitness_score(r[0]);
   if (num_inliers) *num_inliers = r[0].fit_count;
   return HGS_OK;
 } catch (...) {
@@ -1812,8 +1558,7 @@ int hgs_fitness(hgs_handle* h, const float T[16], double max_range, double* scor
 }
 
 int hgs_calc_fitness_score(hgs_handle* h, hgs_cloud* cloud1, hgs_cloud* cloud2, const float relpose[16], double max_range, double* score) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !cloud1 || !cloud2 || cloud1->owner != h || cloud2->owner != h || !relpose || !score) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   hgs_cloud* saved_t = h->target;
@@ -1825,15 +1570,14 @@ int hgs_calc_fitness_score(hgs_handle* h, hgs_cloud* cloud1, hgs_cloud* cloud2, 
   if (rc == HGS_OK) rc = fetch_results(h, 1, r);
   h->target = saved_t;
   if (rc != HGS_OK) return rc;
-  *score = r[0].fit_count > 0 ? r[0].fit_sum / (double)r[0].fit_count : std::numeric_limits<double>::max();
+  *score = fitness_score(r[0]);
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
 }
 
 int hgs_nn_target(hgs_handle* h, const float* q_xyz, size_t nq, size_t stride_bytes, int32_t* idx, float* d2) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || (nq > 0 && (!q_xyz || !idx || !d2)) || stride_bytes < 12) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->target) return HGS_ERR_NO_TARGET;
   if (nq == 0) return HGS_OK;
@@ -1879,8 +1623,7 @@ int hgs_select_best(const hgs_result* records, size_t n, int32_t* best) try {
 
 int hgs_loop_match_batch(hgs_handle* h, hgs_cloud* const* candidates, size_t n_candidates, const float* guesses, double max_range, hgs_result* out,
                          int32_t* best) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || (n_candidates > 0 && (!candidates || !guesses || !out))) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->target) return HGS_ERR_NO_TARGET;
   if (best) *best = -1;
@@ -1922,8 +1665,7 @@ int hgs_comm_get_unique_id(void* id_out) try {
 }
 
 int hgs_comm_init(hgs_handle* h, int32_t rank, int32_t world, const void* unique_id) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !unique_id || world < 1 || rank < 0 || rank >= world) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   if (h->comm) hgs::comm_destroy(h->comm), h->comm = nullptr;
@@ -1938,8 +1680,7 @@ int hgs_comm_init(hgs_handle* h, int32_t rank, int32_t world, const void* unique
 }
 
 int hgs_comm_finalize(hgs_handle* h) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h) return HGS_ERR_INVALID_ARGUMENT;
   if (h->comm) {
     (void)hipSetDevice(h->device);
@@ -2075,8 +1816,7 @@ extern "C" {
 //   4. one D2H of world x max(shard) slots, merge (hgs_debug_merge_shard_records), sequential selection rule.
 int hgs_loop_match_batch_sharded(hgs_handle* h, hgs_cloud* const* candidates, size_t n_mine, const int32_t* candidate_ids, const float* guesses,
                                  size_t n_total, double max_range, hgs_result* all_out, int32_t* best) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   // ---- errors that keep the rank out of the collective: only what a correct caller gets wrong on every rank alike
   if (!h || !all_out || n_total == 0 || n_total > (size_t)1 << 24) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->comm) {
@@ -2217,20 +1957,6 @@ int hgs_loop_match_batch_sharded(hgs_handle* h, hgs_cloud* const* candidates, si
 // ---- prefilter (apps/prefiltering_nodelet.cpp:131-182) -------------------------------------------------------
 namespace {
 
-int scan_u32(hgs_handle* h, const uint32_t* in, uint32_t* out, size_t n) {
-  size_t tmp = 0;
-  if (hgs_exclusive_scan_u32(nullptr, &tmp, in, out, n, h->stream) != 0) {
-    h->err = "rocprim exclusive_scan (size query) failed";
-    return HGS_ERR_HIP;
-  }
-  HGS_HIP(h, h->sort_tmp.reserve(tmp));
-  if (hgs_exclusive_scan_u32(h->sort_tmp.p, &tmp, in, out, n, h->stream) != 0) {
-    h->err = "rocprim exclusive_scan failed";
-    return HGS_ERR_HIP;
-  }
-  return HGS_OK;
-}
-
 // a resident cloud from a device array of {x, y, z, intensity}
 int cloud_from_device(hgs_handle* h, const float4* src, size_t m, hgs_cloud** out) {
   hgs_cloud* c = nullptr;
@@ -2271,8 +1997,7 @@ extern "C" int hgs_prefilter_params_default(hgs_prefilter_params* p) try {
 
 static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const float* deskew_w, double scan_period,
                           hgs_cloud** out) {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !p || !out || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes % 4) != 0 || n > (size_t)1 << 30) return HGS_ERR_INVALID_ARGUMENT;
   if (p->downsample_method < HGS_DOWNSAMPLE_NONE || p->downsample_method > HGS_DOWNSAMPLE_APPROX_VOXELGRID || p->outlier_removal_method < HGS_OUTLIER_NONE ||
       p->outlier_removal_method > HGS_OUTLIER_RADIUS || (p->downsample_method != HGS_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)) ||
@@ -2314,24 +2039,10 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
     const float inv_leaf = 1.0f / (float)p->downsample_resolution;
     launch_pf_bbox(h->stream, cur, d_count, (int)n, d_meta, inline_dist, p->distance_near_thresh, p->distance_far_thresh);
     launch_pf_grid(h->stream, d_meta, inv_leaf);
-    for (int i = 0; i < 2; i++) {
-      HGS_HIP(h, h->sort_keys[i].reserve(n * sizeof(uint64_t)));
-      HGS_HIP(h, h->sort_vals[i].reserve(n * sizeof(uint32_t)));
-    }
+    HGS_TRY(reserve_sort_pairs(h, n));
     launch_pf_voxel_keys(h->stream, cur, d_count, d_meta, inv_leaf, (int)n, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>(), inline_dist,
                          p->distance_near_thresh, p->distance_far_thresh);
-    size_t tmp_bytes = 0;
-    int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                    h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    if (rc == 0) {
-      HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-      rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                  h->sort_vals[1].as<uint32_t>(), n, 0, 32, h->stream);
-    }
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs failed";
-      return HGS_ERR_HIP;
-    }
+    HGS_TRY(sort_pairs(h, n, 0, 32));
     launch_pf_voxel_heads(h->stream, h->sort_keys[1].as<unsigned long long>(), (int)n, h->pf_keep.as<unsigned>(), kVoxelInvalidKey);
     HGS_TRY(scan_u32(h, h->pf_keep.as<uint32_t>(), h->pf_slot.as<uint32_t>(), n));
     // RadiusOutlierRemoval right behind it (the KITTI launch file's prefilter) needs no search tree: the centroids come out in voxel-key order, a point's
@@ -2357,28 +2068,14 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
   if (n > 0 && p->downsample_method == HGS_DOWNSAMPLE_APPROX_VOXELGRID) {
     // pcl::ApproximateVoxelGrid: stable sort by history bucket, runs of equal voxel, eviction order (k_pf_approx_*)
     const float inv_leaf = 1.0f / (float)p->downsample_resolution;
-    for (int i = 0; i < 2; i++) {
-      HGS_HIP(h, h->sort_keys[i].reserve(n * sizeof(uint64_t)));
-      HGS_HIP(h, h->sort_vals[i].reserve(n * sizeof(uint32_t)));
-    }
+    HGS_TRY(reserve_sort_pairs(h, n));
     const size_t o_bucket = align_up(n * sizeof(uint32_t), 256);
     HGS_HIP(h, h->misc.reserve(o_bucket + 2048 * sizeof(uint32_t)));
     unsigned* d_head = h->misc.as<unsigned>();
     unsigned* d_bucket_used = reinterpret_cast<unsigned*>(h->misc.as<char>() + o_bucket);
     unsigned* d_bucket_rank = d_bucket_used + 512;
     launch_pf_approx_keys(h->stream, cur, d_count, inv_leaf, (int)n, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>());
-    size_t tmp_bytes = 0;
-    int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                    h->sort_vals[1].as<uint32_t>(), n, 0, 10, h->stream);
-    if (rc == 0) {
-      HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-      rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                  h->sort_vals[1].as<uint32_t>(), n, 0, 10, h->stream);
-    }
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs failed";
-      return HGS_ERR_HIP;
-    }
+    HGS_TRY(sort_pairs(h, n, 0, 10));
     HGS_HIP(h, hipMemsetAsync(h->pf_keep.p, 0, n * sizeof(uint32_t), h->stream));
     HGS_HIP(h, hipMemsetAsync(d_bucket_used, 0, 1025 * sizeof(uint32_t), h->stream));
     launch_pf_approx_heads(h->stream, cur, h->sort_keys[1].as<unsigned long long>(), h->sort_vals[1].as<unsigned>(), inv_leaf, (int)n, d_head, h->pf_keep.as<unsigned>(),
@@ -2457,8 +2154,7 @@ extern "C" int hgs_prefilter_deskewed(hgs_handle* h, const void* pts, size_t n, 
 }
 
 extern "C" int hgs_cloud_download(hgs_cloud* c, void* out_pts, size_t stride_bytes) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (c && c->owner) api_lock__ = std::unique_lock<std::recursive_mutex>(c->owner->api_mutex);
+  ApiLock lock(c);
   if (!c || !c->owner || stride_bytes < 12 || (stride_bytes % 4) != 0 || (c->n_input > 0 && !out_pts)) return HGS_ERR_INVALID_ARGUMENT;
   hgs_handle* h = c->owner;
   HGS_TRY(set_device(h));
@@ -2485,8 +2181,7 @@ extern "C" int hgs_cloud_download(hgs_cloud* c, void* out_pts, size_t stride_byt
 // ---- map cloud (src/hdl_graph_slam/map_cloud_generator.cpp:13-51) --------------------------------------------
 extern "C" int hgs_map_cloud_generate(hgs_handle* h, hgs_cloud* const* keyframes, const float* poses /* 16 * n, column-major */, size_t n_keyframes,
                                       double resolution, hgs_cloud** out) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !out || (n_keyframes > 0 && (!keyframes || !poses))) return HGS_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   size_t total = 0;
@@ -2546,25 +2241,11 @@ extern "C" int hgs_map_cloud_generate(hgs_handle* h, hgs_cloud* const* keyframes
       h->err = "map cloud: resolution too fine for the extent of the map (the octree would be deeper than 21 levels)";
       return HGS_ERR_INVALID_ARGUMENT;
     }
-    for (int i = 0; i < 2; i++) {
-      HGS_HIP(h, h->sort_keys[i].reserve(total * sizeof(uint64_t)));
-      HGS_HIP(h, h->sort_vals[i].reserve(total * sizeof(uint32_t)));
-    }
+    HGS_TRY(reserve_sort_pairs(h, total));
     // interleaved keys use 3 * depth bits; one more so that the all-ones key of a non-finite point sorts behind every voxel
     const int key_bits = h_oct->n_events > 0 ? 3 * h_oct->events[h_oct->n_events - 1].depth + 1 : 1;
     launch_map_keys(h->stream, all, n, resolution, d_oct, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>());
-    size_t tmp_bytes = 0;
-    int rc = hgs_sort_pairs_u64_u32(nullptr, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                    h->sort_vals[1].as<uint32_t>(), total, 0, key_bits, h->stream);
-    if (rc == 0) {
-      HGS_HIP(h, h->sort_tmp.reserve(tmp_bytes));
-      rc = hgs_sort_pairs_u64_u32(h->sort_tmp.p, &tmp_bytes, h->sort_keys[0].as<uint64_t>(), h->sort_keys[1].as<uint64_t>(), h->sort_vals[0].as<uint32_t>(),
-                                  h->sort_vals[1].as<uint32_t>(), total, 0, key_bits, h->stream);
-    }
-    if (rc != 0) {
-      h->err = "rocprim radix_sort_pairs failed";
-      return HGS_ERR_HIP;
-    }
+    HGS_TRY(sort_pairs(h, total, 0, key_bits));
     launch_pf_voxel_heads(h->stream, h->sort_keys[1].as<unsigned long long>(), n, h->pf_keep.as<unsigned>(), kMapInvalidKey);
     HGS_TRY(scan_u32(h, h->pf_keep.as<uint32_t>(), h->pf_slot.as<uint32_t>(), total));
     launch_map_centers(h->stream, h->sort_keys[1].as<unsigned long long>(), h->pf_keep.as<unsigned>(), h->pf_slot.as<unsigned>(), n, resolution, d_oct,
@@ -2610,23 +2291,6 @@ bool floor_params_valid(const hgs_floor_params* p) {
          std::isfinite(p->floor_normal_thresh) && p->floor_normal_thresh >= 0 && std::isfinite(p->normal_filter_thresh) && p->normal_filter_thresh >= 0 &&
          p->normal_k >= 3 && p->normal_k <= 64 && p->ransac_max_iterations >= 0 && std::isfinite(p->ransac_distance_threshold) && p->ransac_distance_threshold >= 0 &&
          p->ransac_probability > 0 && p->ransac_probability < 1;
-}
-
-FloorConsts floor_consts(const hgs_floor_params* p) {
-  FloorConsts c{};
-  // tilt_matrix (:112-113): the angle is a float (Eigen::AngleAxisf); z' = (R p).z = -sin * x + cos * z, r = R^-1 e_z = (-sin, 0, cos)
-  const double angle = (double)(float)(p->tilt_deg * M_PI / 180.0);
-  c.rx = p->tilt_deg == 0.0 ? 0.f : -(float)std::sin(angle);
-  c.rz = p->tilt_deg == 0.0 ? 1.f : (float)std::cos(angle);
-  c.nrx = (double)c.rx, c.nrz = (double)c.rz;
-  c.clip_lo = (float)(p->sensor_height + p->height_clip_range);  // :118
-  c.clip_hi = (float)(p->sensor_height - p->height_clip_range);  // :119
-  c.normal_cos = std::cos(p->normal_filter_thresh * M_PI / 180.0);  // :228
-  c.dist_thresh = p->ransac_distance_threshold;
-  c.log_prob = std::log(1.0 - p->ransac_probability);
-  c.max_iterations = p->ransac_max_iterations;
-  c.seed = p->seed;
-  return c;
 }
 
 struct FloorWork {
@@ -2808,8 +2472,7 @@ int detect_floor_locked(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params*
 }  // namespace
 
 extern "C" int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (filtered_out) *filtered_out = nullptr;
   if (inliers_out) *inliers_out = nullptr;
   if (!h || !cloud || !p || !out || cloud->owner != h || !floor_params_valid(p)) return HGS_ERR_INVALID_ARGUMENT;
@@ -2828,8 +2491,7 @@ extern "C" int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor
 }
 
 extern "C" int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint8_t* keep_clip, uint8_t* keep_normal, double* normals3) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !cloud || !p || cloud->owner != h || !floor_params_valid(p)) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   FloorWork w;
@@ -2841,8 +2503,7 @@ extern "C" int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs
 }
 
 extern "C" int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint32_t i0, uint32_t n, int32_t* counts, double* coeffs4) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !cloud || !p || cloud->owner != h || !floor_params_valid(p) || (n > 0 && !counts) || (uint64_t)i0 + n > 0x7fffffffull) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   const int chunk = std::max(1, std::min(kFloorMaxChunk, h->floor_chunk));
@@ -2865,8 +2526,7 @@ extern "C" int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, co
 }
 
 int hgs_profile_enable(hgs_handle* h, int enabled) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h) return HGS_ERR_INVALID_ARGUMENT;
   h->profiling = enabled != 0;
   return HGS_OK;
@@ -2875,8 +2535,7 @@ int hgs_profile_enable(hgs_handle* h, int enabled) try {
 }
 
 int hgs_profile_read(hgs_handle* h, double* ms, uint64_t* launches, int reset) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
@@ -2900,8 +2559,7 @@ int hgs_profile_read(hgs_handle* h, double* ms, uint64_t* launches, int reset) t
 }
 
 int hgs_synchronize(hgs_handle* h) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h) return HGS_ERR_INVALID_ARGUMENT;
   HGS_TRY(set_device(h));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
@@ -2912,8 +2570,7 @@ int hgs_synchronize(hgs_handle* h) try {
 
 // ---- stage-level hooks for the parity tests ---------------------------------------------------------------
 int hgs_debug_target_covariances(hgs_handle* h, float* out6) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !out6) return HGS_ERR_INVALID_ARGUMENT;
   if (!h->target) return HGS_ERR_NO_TARGET;
   HGS_TRY(set_device(h));
@@ -2941,8 +2598,7 @@ int hgs_debug_target_covariances(hgs_handle* h, float* out6) try {
 }
 
 int hgs_debug_gicp_linearize(hgs_handle* h, const double T12[12], double* H36, double* b6, double* err, int32_t* corr) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !T12 || !H36 || !b6 || !err) return HGS_ERR_INVALID_ARGUMENT;
   if (h->prm.method != HGS_FAST_GICP && h->prm.method != HGS_FAST_VGICP) return HGS_ERR_UNSUPPORTED;
   if (!h->target) return HGS_ERR_NO_TARGET;
@@ -3003,8 +2659,7 @@ int hgs_debug_gicp_linearize(hgs_handle* h, const double T12[12], double* H36, d
 }
 
 int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17, int32_t* corr) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !T12 || !sums17) return HGS_ERR_INVALID_ARGUMENT;
   if (h->prm.method != HGS_ICP) return HGS_ERR_UNSUPPORTED;
   if (!h->target) return HGS_ERR_NO_TARGET;
@@ -3060,8 +2715,7 @@ int hgs_debug_icp_correspond(hgs_handle* h, const double T12[12], double* sums17
 
 int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_in[12], double mse_prev, int32_t iterations_in, double T12_out[12],
                        int32_t flags3[3], double* mse) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !sums17 || !T12_in || !T12_out || !flags3 || !mse) return HGS_ERR_INVALID_ARGUMENT;
   if (h->prm.method != HGS_ICP) return HGS_ERR_UNSUPPORTED;
   if (!h->source) return HGS_ERR_NO_SOURCE;  // (k_icp_solve takes its tile count from the source's nvalid)
@@ -3096,8 +2750,7 @@ int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_
 }
 
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !n_cells) return HGS_ERR_INVALID_ARGUMENT;
   if (h->prm.method != HGS_NDT_OMP) return HGS_ERR_UNSUPPORTED;
   if (!h->target) return HGS_ERR_NO_TARGET;
@@ -3111,7 +2764,7 @@ int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3
   const int n = std::min<int>(meta.ndt_ncells, cap);
   if (n <= 0) return HGS_OK;
   std::vector<NdtCellRec> cells(n);
-  HGS_HIP(h, hipMemcpyAsync(cells.data(), t->ndt_cells, (size_t)n * sizeof(NdtCellRec), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipMemcpyAsync(cells.data(), t->ndt.cells, (size_t)n * sizeof(NdtCellRec), hipMemcpyDeviceToHost, h->stream));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < n; i++) {
     int key;
@@ -3135,8 +2788,7 @@ int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3
 }
 
 int hgs_debug_ndt_derivatives(hgs_handle* h, const double p6[6], double* score, double* g6, double* H36) try {
-  std::unique_lock<std::recursive_mutex> api_lock__;
-  if (h) api_lock__ = std::unique_lock<std::recursive_mutex>((h)->api_mutex);
+  ApiLock lock(h);
   if (!h || !p6 || !score || !g6 || !H36) return HGS_ERR_INVALID_ARGUMENT;
   if (h->prm.method != HGS_NDT_OMP) return HGS_ERR_UNSUPPORTED;
   if (!h->target) return HGS_ERR_NO_TARGET;
@@ -3148,7 +2800,7 @@ int hgs_debug_ndt_derivatives(hgs_handle* h, const double p6[6], double* score, 
   std::vector<hgs_cloud*> src{s};
   const CloudDesc* d_descs = nullptr;
   HGS_TRY(upload_descs(h, src, false, &d_descs, nullptr));
-  const NdtConsts c = ndt_consts(h->prm);
+  const NdtConsts c = engine_ndt_consts(h->prm);
   HGS_HIP(h, h->states.reserve(sizeof(NdtState)));
   HGS_HIP(h, h->angles.reserve(sizeof(NdtAngles)));
   HGS_HIP(h, h->ndt_accum.reserve(sizeof(NdtAccum)));

@@ -18,6 +18,8 @@
 #include "../../hdl_graph_slam_amd/csrc/hgs_gicp.h"
 #include "../../hdl_graph_slam_amd/csrc/hgs_ndt.h"
 #include "../../hdl_graph_slam_amd/csrc/hgs_vgicp.h"
+using float4 = hgs::Float4;  // (hgs_floor.h, which hgs_consts.h pulls in, spells the HIP type)
+#include "../../hdl_graph_slam_amd/csrc/hgs_consts.h"
 #include "../../include/hgs_registration.h"
 
 using namespace hgs;
@@ -153,16 +155,6 @@ static void knn_cov(ECloud& c, int k, int reg_method) {
 static Sym3 load_cov(const std::vector<Float4>& cov, int i) {
   const Float4 a = cov[2 * i], b = cov[2 * i + 1];
   return sym3_from_floats(a.x, a.y, a.z, a.w, b.x, b.y);
-}
-
-static GicpConsts gicp_consts(const hgs_params& p) {
-  GicpConsts c;
-  c.max_corr2 = p.max_correspondence_distance * p.max_correspondence_distance;
-  c.search_bound2 = c.max_corr2 >= (double)FLT_MAX ? FLT_MAX : nextafterf((float)c.max_corr2, FLT_MAX);
-  c.rotation_eps = p.rotation_epsilon, c.translation_eps = p.transformation_epsilon;
-  c.lm_init_lambda_factor = p.lm_init_lambda_factor, c.lm_max_iterations = p.lm_max_iterations, c.max_iterations = p.max_iterations;
-  c.k_correspondences = p.correspondence_randomness;
-  return c;
 }
 
 // k_gicp_linearize over all tiles, partials summed in tile order (k_gicp_solve)
@@ -304,17 +296,6 @@ static void ndt_derivatives(const ECloud& src, const ENdt& e, const NdtAngles& a
   }
   for (int k = 0; k < kAccNdt; k++) acc_out[k] = total[k];
 }
-static NdtConsts ndt_consts(const hgs_params& p) {
-  NdtConsts c;
-  const double c1 = 10.0 * (1 - p.ndt_outlier_ratio), c2 = p.ndt_outlier_ratio / std::pow(p.resolution, 3), d3 = -std::log(c2);
-  c.gauss_d1 = -std::log(c1 + c2) - d3;
-  c.gauss_d2 = -2 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / c.gauss_d1);
-  c.step_size = p.ndt_step_size, c.trans_eps = p.transformation_epsilon, c.max_iterations = p.max_iterations;
-  c.search = p.neighbor_search == HGS_DIRECT1 ? 1 : (p.neighbor_search == HGS_KDTREE ? 0 : 2);
-  c.upstream_hd1_sign = p.ndt_upstream_hd1_sign, c.pad = 0;
-  c.kdtree_radius2 = (float)(p.resolution * p.resolution), c.line_search = p.ndt_line_search ? 1 : 0;
-  return c;
-}
 
 // ---- VGICP target (k_vgicp_grid_params / k_vgicp_cell_keys / sort / k_vgicp_build_cells)
 static void vgicp_build(ENdt& e, const ECloud& c, double resolution) {
@@ -364,13 +345,6 @@ static void vgicp_build(ENdt& e, const ECloud& c, double resolution) {
     i = j;
   }
   g.hash_keys = e.hash_keys.data(), g.hash_vals = e.hash_vals.data(), g.cells = e.cells.data();
-}
-static VgicpConsts vgicp_consts(const hgs_params& p) {
-  VgicpConsts c;
-  c.resolution = p.resolution;
-  c.search = p.neighbor_search == HGS_DIRECT27 ? 3 : (p.neighbor_search == HGS_DIRECT7 ? 2 : 1);
-  c.pad = 0;
-  return c;
 }
 // k_vgicp_linearize over all tiles, partials summed in tile order
 static void vgicp_linearize(ECloud& src, const ENdt& e, const Pose& T, const VgicpConsts& c, double* acc_out) {

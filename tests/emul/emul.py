@@ -13,7 +13,7 @@ _ROOT = os.path.dirname(os.path.dirname(_HERE))
 
 
 def build():
-    srcs = [os.path.join(_HERE, "emul.cpp")] + [os.path.join(_ROOT, "hdl_graph_slam_amd", "csrc", f) for f in ("hgs_math.h", "hgs_bvh.h", "hgs_gicp.h", "hgs_ndt.h", "hgs_vgicp.h")]
+    srcs = [os.path.join(_HERE, "emul.cpp")] + [os.path.join(_ROOT, "hdl_graph_slam_amd", "csrc", f) for f in ("hgs_math.h", "hgs_bvh.h", "hgs_gicp.h", "hgs_ndt.h", "hgs_vgicp.h", "hgs_icp.h", "hgs_floor.h", "hgs_consts.h")]
     if not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs):
         subprocess.run(["g++", "-O2", "-march=x86-64-v3", "-mfma", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas",
                         "-o", _LIB, srcs[0]], check=True)

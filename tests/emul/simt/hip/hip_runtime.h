@@ -35,6 +35,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <functional>
 
 // ------------------------------------------------------------------------------------------------ language
@@ -73,6 +74,7 @@ struct Thread {
 extern thread_local Thread* g_cur;
 extern unsigned long long g_record_fetches, g_waves_launched;   // statistics (fetch_record calls of lane 0, waves started)
 extern thread_local Idx g_block, g_block_dim, g_grid_dim;
+extern std::atomic<long long> g_live_blocks, g_live_streams, g_live_events;  // objects the runtime calls below have handed out and not taken back (simt_read_live_objects)
 
 // all-to-all exchange of one 64-bit value among the live lanes of the calling lane's wave; returns the mask of lanes that took
 // part, out[l] = value of lane l.  `kind` must agree among the participants (a mismatch means divergent collectives).
@@ -269,9 +271,11 @@ static inline hipError_t hipGetDeviceCount(int* n) {
 template <typename T>
 static inline hipError_t hipMalloc(T** p, size_t bytes) {
   *p = (T*)aligned_alloc(256, (bytes + 255) / 256 * 256 + 256);
+  if (*p) simt::g_live_blocks++;
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static inline hipError_t hipFree(void* p) {
+  if (p) simt::g_live_blocks--;
   free(p);
   return hipSuccess;
 }
@@ -291,10 +295,12 @@ static inline hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t 
 }
 static inline hipError_t hipStreamCreate(hipStream_t* s) {
   *s = malloc(1);
+  simt::g_live_streams++;
   return hipSuccess;
 }
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { return hipStreamCreate(s); }
 static inline hipError_t hipStreamDestroy(hipStream_t s) {
+  simt::g_live_streams--;
   free(s);
   return hipSuccess;
 }
@@ -303,10 +309,12 @@ static inline hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 static inline hipError_t hipEventCreate(hipEvent_t* e) {
   *e = malloc(1);
+  simt::g_live_events++;
   return hipSuccess;
 }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 static inline hipError_t hipEventDestroy(hipEvent_t e) {
+  simt::g_live_events--;
   free(e);
   return hipSuccess;
 }

@@ -46,6 +46,7 @@ namespace simt {
 
 thread_local Thread* g_cur = nullptr;
 unsigned long long g_record_fetches = 0, g_waves_launched = 0;
+std::atomic<long long> g_live_blocks{0}, g_live_streams{0}, g_live_events{0};
 thread_local Idx g_block = {0, 0, 0}, g_block_dim = {1, 1, 1}, g_grid_dim = {1, 1, 1};
 
 namespace {
@@ -288,6 +289,11 @@ extern "C" int hgs_exclusive_scan_u32(void* temp, size_t* temp_bytes, const uint
 extern "C" void simt_read_counters(unsigned long long* out2) {
   out2[0] = simt::g_record_fetches, out2[1] = simt::g_waves_launched;
   simt::g_record_fetches = 0, simt::g_waves_launched = 0;
+}
+
+// live objects of the emulated runtime: {memory blocks (hipMalloc + hipHostMalloc), streams, events}; not reset on read
+extern "C" void simt_read_live_objects(long long* out3) {
+  out3[0] = simt::g_live_blocks, out3[1] = simt::g_live_streams, out3[2] = simt::g_live_events;
 }
 
 // ------------------------------------------------------------------------------------------------ hgs_comm.h on the host
