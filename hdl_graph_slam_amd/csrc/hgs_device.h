@@ -223,7 +223,7 @@ void launch_pf_approx_centroids(hipStream_t s, const float4* pts, const unsigned
                                 const unsigned* evict_rank, const unsigned* bucket_rank, int cap, float4* out, int* count_out);
 void launch_pf_radius_flags(hipStream_t s, CloudDesc d, float r2, int min_neighbors, unsigned* keep);
 void launch_pf_mean_knn_dist(hipStream_t s, CloudDesc d, int mean_k, double* dist);
-void launch_pf_statistical(hipStream_t s, const double* dist, int n, double* stats, double stddev_mul, unsigned* keep);
+void launch_pf_statistical(hipStream_t s, CloudDesc d, const double* dist, double* stats, double stddev_mul, unsigned* keep);
 void launch_pf_to_cloud(hipStream_t s, const float4* in, int n, float4* raw, float* intensity, CloudMeta* meta_to_reset, const CloudDesc* desc = nullptr, CloudDesc* desc_out = nullptr);
 
 // floor detection (apps/floor_detection_nodelet.cpp:110-238; hgs_floor.h)

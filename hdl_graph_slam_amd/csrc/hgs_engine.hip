@@ -2101,7 +2101,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
     std::vector<hgs_cloud*> one{c};
     int rc = ensure_index(h, one);
     if (rc == HGS_OK) {
-      hipError_t e = hipMemsetAsync(h->pf_keep.p, 0, m * sizeof(uint32_t), h->stream);  // non-finite points are dropped
+      hipError_t e = hipMemsetAsync(h->pf_keep.p, 0, m * sizeof(uint32_t), h->stream);  // non-finite points are dropped: only valid points get a flag
       if (e != hipSuccess) rc = HGS_ERR_HIP;
     }
     if (rc == HGS_OK) {
@@ -2113,7 +2113,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
         if (e != hipSuccess) rc = HGS_ERR_HIP;
         else {
           launch_pf_mean_knn_dist(h->stream, c->desc, p->statistical_mean_k, h->pf_dist.as<double>());
-          launch_pf_statistical(h->stream, h->pf_dist.as<double>(), (int)m, d_stats, p->statistical_stddev, h->pf_keep.as<unsigned>());
+          launch_pf_statistical(h->stream, c->desc, h->pf_dist.as<double>(), d_stats, p->statistical_stddev, h->pf_keep.as<unsigned>());
         }
       }
     }

@@ -2324,8 +2324,13 @@ __global__ void k_pf_grid(unsigned* meta, float inv_leaf) {
     im[6 + k] = (int)floorf(ord2f(meta[k]) * inv_leaf);
     div[k] = (long long)(int)floorf(ord2f(meta[3 + k]) * inv_leaf) - im[6 + k] + 1;
   }
-  im[12] = div[0] * div[1] * div[2] > 2147483647LL ? 1 : 0;
-  im[9] = 1, im[10] = (int)div[0], im[11] = (int)(div[0] * div[1]);
+  // more than INT_MAX cells?  Factor by factor: the product of the three wraps 64 bits from 2^21 cells per axis on (every div is >= 1)
+  const long long kMaxCells = 2147483647LL;
+  bool over = div[0] > kMaxCells;
+  if (!over) over = div[1] > kMaxCells / div[0];
+  if (!over) over = div[2] > kMaxCells / (div[0] * div[1]);
+  im[12] = over ? 1 : 0;
+  im[9] = 1, im[10] = over ? 0 : (int)div[0], im[11] = over ? 0 : (int)(div[0] * div[1]);  // (not read when im[12] is set: k_pf_voxel_keys)
 }
 __global__ __launch_bounds__(kBlock) void k_pf_voxel_keys(const float4* __restrict__ pts, const int* __restrict__ count, const unsigned* __restrict__ meta, float inv_leaf,
                                                           int cap, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, int dist_filter, double near_thresh,
@@ -2636,7 +2641,8 @@ void launch_pf_mean_knn_dist(hipStream_t s, CloudDesc d, int mean_k, double* dis
   else if (mean_k + 1 <= 32) hipLaunchKernelGGL(k_pf_mean_knn_dist<32>, grid, block, 0, s, d, mean_k, dist);
   else hipLaunchKernelGGL(k_pf_mean_knn_dist<64>, grid, block, 0, s, d, mean_k < 63 ? mean_k : 63, dist);
 }
-// pass 2: sum and sum of squares of dist[0..n) in a fixed order (one block: per-thread strided sums, tree over the block)
+// pass 2: sum and sum of squares of dist[0..n) in a fixed order (one block: per-thread strided sums, tree over the block).  n is the INPUT count: a
+// non-finite point's entry is the 0.0 the caller cleared dist[] to, which changes neither sum — the statistics are those of the valid points
 __global__ __launch_bounds__(kBlock) void k_pf_dist_stats(const double* __restrict__ dist, int n, double* __restrict__ out2) {
   __shared__ double s1[kBlock], s2[kBlock];
   double a = 0.0, b = 0.0;
@@ -2652,22 +2658,26 @@ __global__ __launch_bounds__(kBlock) void k_pf_dist_stats(const double* __restri
   }
   if (threadIdx.x == 0) out2[0] = s1[0], out2[1] = s2[0];
 }
-// pass 3: keep[i] = dist[i] <= mean + mul * stddev (sample standard deviation)
-__global__ __launch_bounds__(kBlock) void k_pf_statistical_flags(const double* __restrict__ dist, int n, const double* __restrict__ stats, double stddev_mul,
+// pass 3: keep[i] = dist[i] <= mean + mul * stddev (sample standard deviation), mean and stddev over the cloud's nvalid finite points.  One thread per
+// Hilbert-sorted point, as in pass 1, the flag at the point's ORIGINAL index: a non-finite point gets none and keeps the 0 the caller cleared keep[] to
+// (pcl::StatisticalOutlierRemoval divides by the valid count too, but keeps the non-finite points of a non-dense cloud; here they are dropped)
+__global__ __launch_bounds__(kBlock) void k_pf_statistical_flags(CloudDesc d, const double* __restrict__ dist, const double* __restrict__ stats, double stddev_mul,
                                                                  unsigned* __restrict__ keep) {
   HGS_FP_STRICT
+  const int n = d.meta->nvalid;
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
+  const int orig = __float_as_int(d.pts[i].w);
   const double dn = (double)n;
   const double mean = stats[0] / dn;
   const double var = n > 1 ? (stats[1] - stats[0] * stats[0] / dn) / (dn - 1.0) : 0.0;
   const double thr = mean + stddev_mul * sqrt(var);
-  keep[i] = dist[i] <= thr ? 1u : 0u;
+  keep[orig] = dist[orig] <= thr ? 1u : 0u;
 }
-void launch_pf_statistical(hipStream_t s, const double* dist, int n, double* stats, double stddev_mul, unsigned* keep) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_pf_dist_stats, dim3(1), dim3(kBlock), 0, s, dist, n, stats);
-  hipLaunchKernelGGL(k_pf_statistical_flags, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, dist, n, stats, stddev_mul, keep);
+void launch_pf_statistical(hipStream_t s, CloudDesc d, const double* dist, double* stats, double stddev_mul, unsigned* keep) {
+  if (d.n_input <= 0) return;
+  hipLaunchKernelGGL(k_pf_dist_stats, dim3(1), dim3(kBlock), 0, s, dist, d.n_input, stats);
+  hipLaunchKernelGGL(k_pf_statistical_flags, dim3((d.n_input + kBlock - 1) / kBlock), dim3(kBlock), 0, s, d, dist, stats, stddev_mul, keep);
 }
 
 // ------------------------------------------------------------------------------------------------ map cloud (next row f3)

@@ -17,6 +17,8 @@
 //   StatisticalOutlierRemoval: d_i = mean distance (sqrt of float d2, accumulated in double) to the mean_k nearest
 //     OTHER points (k+1 search, self dropped); mean and sample stddev over all d_i in double;
 //     keep p iff d_i <= mean + stddev_mul * stddev.
+//   Non-finite points take no part in either outlier filter (OCloud holds the finite points): not searched, not counted in the
+//     statistics, not in the output.  (PCL passes the non-finite points of a non-dense cloud through StatisticalOutlierRemoval.)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -99,7 +101,9 @@ inline bool pf_voxelgrid(const std::vector<PfPoint>& in, double leaf, std::vecto
     min_b[k] = (int)std::floor(mn[k] * inv);
     div[k] = (long long)(int)std::floor(mx[k] * inv) - min_b[k] + 1;
   }
-  if (div[0] * div[1] * div[2] > 2147483647LL) return false;
+  // factor by factor: the product of the three wraps 64 bits from 2^21 cells per axis on (every div is >= 1)
+  const long long max_cells = 2147483647LL;
+  if (div[0] > max_cells || div[1] > max_cells / div[0] || div[2] > max_cells / (div[0] * div[1])) return false;
   struct KV {
     uint32_t key;
     uint32_t idx;

@@ -1,11 +1,14 @@
 """Prefilter ("next" row f2: apps/prefiltering_nodelet.cpp:131-182): the oracle against an independent numpy
-restatement, the ABI, and (-m gpu) the HIP pipeline against the oracle — point for point, in order."""
+restatement (the outlier filters: tests/prefilter_reference.py), the ABI, and (-m gpu) the HIP pipeline against the oracle — point for point, in
+order; the edge inputs of tests/prefilter_checks.py, which tests/test_simt_kernels_host.py runs on the host emulation."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import oracle as O
+import prefilter_checks as PFC
+import prefilter_reference as PR
 from hdl_graph_slam_amd import synth
 
 
@@ -225,35 +228,7 @@ def test_large_upload_round_trip_through_the_pack_pool(n, layout):
     reg.close()
 
 
-def _py_approx_voxelgrid(cloud, leaf):
-    """pcl::ApproximateVoxelGrid as PCL runs it — a plain sequential loop over the points with the 512-entry history table —
-    independent of oracle/prefilter.hpp and of the device's sort-based form."""
-    inv = np.float32(1.0) / np.float32(leaf)
-    hist = {}
-    out = []
-
-    def flush(e):
-        out.append((e[4] / np.float32(e[3])).astype(np.float32))
-
-    for r in cloud:
-        p = np.array([r["x"], r["y"], r["z"], r["intensity"]], np.float32)
-        if not np.isfinite(p[:3]).all():
-            continue
-        ix, iy, iz = (int(np.floor(np.float32(p[k] * inv))) for k in range(3))
-        h = (ix * 7171 + iy * 3079 + iz * 4231) & 511
-        e = hist.get(h)
-        if e is not None and e[3] and (e[0], e[1], e[2]) != (ix, iy, iz):
-            flush(e)
-            e = None
-        if e is None:
-            e = [ix, iy, iz, 0, np.zeros(4, np.float32)]
-            hist[h] = e
-        e[3] += 1
-        e[4] = (e[4] + p).astype(np.float32)
-    for h in sorted(hist):
-        if hist[h][3]:
-            flush(hist[h])
-    return np.array(out, np.float32).reshape(-1, 4)
+_py_approx_voxelgrid = PR.approx_voxelgrid   # the sequential filter, independent of the oracle and of the device's sort-based form
 
 
 @pytest.mark.parametrize("leaf", [0.1, 0.5, 2.0])
@@ -388,3 +363,83 @@ def test_hip_deskewed_prefilter_matches_oracle():
     from hdl_graph_slam_amd import _lib as L
     from hdl_graph_slam_amd.registration import RegistrationHIP
     _check_deskewed_prefilter(lambda: RegistrationHIP(L.default_params(L.HGS_FAST_GICP)))
+
+
+# ---- the outlier filters and the edge inputs of prefilter_checks.py ---------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(PFC.outlier_cases()))
+def test_oracle_outlier_removal_matches_the_numpy_reference(name):
+    """oracle/prefilter.hpp's RadiusOutlierRemoval and StatisticalOutlierRemoval (kd-tree searches) against the brute-force restatement of
+    prefilter_reference.py on every case the device is compared with the oracle on: the same points, in order, bit for bit.  A statistical point within
+    1e-12 of the threshold could take either flag depending on the order of the sums; the cases are chosen so that there is none (asserted), and the
+    reference with its sums taken from the last point to the first gives the same flags — so nothing is left out of the comparison."""
+    cloud, fields = PFC.outlier_cases()[name]
+    p = PFC.oracle_params(**fields)
+    got = O.prefilter(cloud, p)
+    front = PFC.oracle_params(**fields)
+    front.outlier_removal_method = 0
+    pts = O.prefilter(cloud, front)      # what reaches the outlier filter (distance filter and downsampling have restatements of their own above)
+    if p.outlier_removal_method == PFC.RADIUS:
+        ref = PR.radius_outlier_removal(pts, p.radius_radius, p.radius_min_neighbors)
+    else:
+        keep, d, thr = PR.statistical_outlier_details(pts, p.statistical_mean_k, p.statistical_stddev)
+        keep_r, d_r, thr_r = PR.statistical_outlier_details(pts, p.statistical_mean_k, p.statistical_stddev, reverse_sums=True)
+        band = int(PR.threshold_band(d, thr).sum()) if len(d) > 2 else 0      # (two points: d_0 = d_1 = the threshold exactly, in either order)
+        print(f"{name}: {len(d)} finite points, threshold {thr!r} (reversed sums {thr_r!r}), {band} within 1e-12 of it, {int(keep.sum())} kept")
+        assert band == 0 and np.array_equal(keep, keep_r), name
+        ref = PR.xyz_intensity(pts)[keep]
+    assert got.shape == ref.shape and np.array_equal(got, ref), (name, got.shape, ref.shape)
+
+
+def test_outlier_cases_exercise_what_they_are_meant_to():
+    PFC.check_outlier_cases_are_not_trivial()
+
+
+def test_reference_fused_multiply_add_is_correctly_rounded():
+    """prefilter_reference.fmaf32 against exact rational arithmetic: random operands of mixed magnitudes, and two where a * b + c lies 2^-70 off a float
+    tie — a double multiply-add rounded to float (two roundings) gets those wrong."""
+    from fractions import Fraction
+    rng = np.random.default_rng(0)
+    a = rng.normal(0, 1, 2000).astype(np.float32)
+    b = rng.normal(0, 1, 2000).astype(np.float32)
+    c = (rng.normal(0, 1, 2000) * 10.0 ** rng.integers(-12, 12, 2000)).astype(np.float32)
+    u = 2.0 ** -23
+    a = np.concatenate([a, np.float32([1 + u, 1 + u])])
+    b = np.concatenate([b, np.float32([(1 - u) * 2.0 ** -24, -(1 - u) * 2.0 ** -24])])
+    c = np.concatenate([c, np.float32([1 + u, 1 + u])])
+    got = PR.fmaf32(a, b, c)
+    assert got[-2] == got[-1] == np.float32(1 + u)
+    naive = (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+    assert naive[-2] != got[-2] and naive[-1] != got[-1]      # what the correction is for
+    for x, y, z, g in zip(a, b, c, got):
+        exact = Fraction(float(x)) * Fraction(float(y)) + Fraction(float(z))
+        near = np.float32(float(exact))
+        cands = sorted({float(np.nextafter(near, np.float32(-np.inf))), float(near), float(np.nextafter(near, np.float32(np.inf)))})
+        err = [abs(Fraction(v) - exact) for v in cands]
+        best = [v for v, e in zip(cands, err) if e == min(err)]
+        if len(best) > 1:                                  # a tie: to even
+            best = [v for v in best if (int(np.float32(v).view(np.uint32)) & 1) == 0]
+        assert float(g) == best[0], (x, y, z, g, best)
+
+
+def _hip_engine(params):
+    from hdl_graph_slam_amd import _lib as L
+    from hdl_graph_slam_amd.registration import RegistrationHIP
+    p = L.HgsParams()
+    for name, _ in L.HgsParams._fields_:
+        setattr(p, name, getattr(params, name))
+    return RegistrationHIP(p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(PFC.outlier_cases()))
+def test_hip_outlier_removal_edge_inputs(name):
+    """k_pf_mean_knn_dist<16 | 32 | 64>, k_pf_dist_stats, k_pf_statistical_flags, k_pf_radius_flags, k_pf_grid_radius_flags at the bounds of mean_k, small
+    clouds, coincident points and non-finite points (prefilter_checks.outlier_cases)."""
+    PFC.check_outlier_case(_hip_engine, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("check", ["voxelgrid_one_long_run", "voxelgrid_block_multiples", "all_nonfinite_cloud", "distance_thresholds_are_strict",
+                                   "voxel_index_overflow", "approx_voxelgrid_edges", "deskew_with_a_nonfinite_record", "arguments"])
+def test_hip_prefilter_edge_inputs(check):
+    getattr(PFC, "check_" + check)(_hip_engine)

@@ -11,6 +11,7 @@ import pytest
 
 import oracle as O
 import parity_checks as PC
+import prefilter_checks as PFC
 from hdl_graph_slam_amd import synth
 
 simt = pytest.importorskip("emul.simt", reason="needs tests/emul")
@@ -607,6 +608,18 @@ def test_approx_voxelgrid_in_eviction_order():
 
 def test_ndt_edge_cases():
     PC.check_ndt_edge_cases(_engine)
+
+
+@pytest.mark.parametrize("name", sorted(PFC.outlier_cases()))
+def test_prefilter_outlier_removal_edge_inputs(name):
+    """The prefilter's outlier kernels at the bounds of mean_k, small clouds, coincident and non-finite points (prefilter_checks.outlier_cases)."""
+    PFC.check_outlier_case(_engine, name)
+
+
+@pytest.mark.parametrize("check", ["voxelgrid_one_long_run", "voxelgrid_block_multiples", "all_nonfinite_cloud", "distance_thresholds_are_strict",
+                                   "voxel_index_overflow", "approx_voxelgrid_edges", "deskew_with_a_nonfinite_record", "arguments"])
+def test_prefilter_edge_inputs(check):
+    getattr(PFC, "check_" + check)(_engine)
 
 
 # ---- hgs_loop_match_batch_sharded with TWO ranks: two engines driven from two host threads of this process, the emulated
