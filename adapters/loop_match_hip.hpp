@@ -166,6 +166,80 @@ public:
     if (!candidates.empty() && hgs_select_best(records->data(), records->size(), &best) != HGS_OK) last_error_ += "hgs_select_best failed; ", best = -1;
     return best;
   }
+  // The candidates of SEVERAL new keyframes of one graph update (LoopDetector::detect, loop_detector.hpp:57-68, calls matching once per new keyframe):
+  // group g registers groups[g].candidates against the keyframe groups[g] describes; (*records)[g][i] and (*best)[g] are what match() gives for that group
+  // alone, bit for bit.  One engine: ONE hgs_loop_match_groups over the resident keyframes — the new keyframes become resident like the candidates (they are
+  // the next updates' candidates), under the same LRU budget.  Several engines: match() per group.  Returns false when a call was refused or failed
+  // (last_error() says why): the caller falls back to its sequential loop, as after a match() with failed_engines() > 0.  Never throws.
+  struct Group {
+    long keyframe_id;       // the new keyframe (the group's target)
+    const void* points;     // only read when it is not resident yet
+    size_t n;
+    size_t stride_bytes;
+    std::vector<Candidate> candidates;
+  };
+  bool match_groups(const std::vector<Group>& groups, double max_range, std::vector<std::vector<hgs_result>>* records, std::vector<int>* best) {
+    records->assign(groups.size(), {});
+    best->assign(groups.size(), -1);
+    if (engines_.size() > 1 || !use_grouped_call(groups)) {
+      bool ok = true;
+      std::string errors;
+      for (size_t g = 0; g < groups.size(); g++) {
+        if (groups[g].candidates.empty()) continue;
+        (*best)[g] = match(groups[g].points, groups[g].n, groups[g].stride_bytes, groups[g].candidates, max_range, &(*records)[g]);
+        if (failed_engines_ > 0) ok = false, errors += last_error_;
+      }
+      if (!ok) last_error_ = errors;
+      return ok;
+    }
+    Engine& eng = engines_[0];
+    const uint64_t tick = ++tick_;
+    last_error_.clear();
+    failed_engines_ = 0, used_engines_ = 1;
+    bool ok = true;
+    try {
+      auto resident = [&](long id, const void* pts, size_t n, size_t stride) {
+        auto it = eng.clouds.find(id);
+        if (it == eng.clouds.end()) {
+          hgs_cloud* cl = nullptr;
+          check(eng, hgs_cloud_create(eng.h, pts, n, stride, &cl));
+          it = eng.clouds.emplace(id, Resident{cl, 0, 0}).first;
+        }
+        it->second.last_used = tick;
+        return it->second.cloud;
+      };
+      std::vector<hgs_cloud*> targets(groups.size(), nullptr), clouds;
+      std::vector<size_t> offsets(groups.size() + 1, 0);
+      std::vector<float> guesses;
+      for (size_t g = 0; g < groups.size(); g++) {
+        const Group& grp = groups[g];
+        offsets[g + 1] = offsets[g] + grp.candidates.size();
+        if (grp.candidates.empty()) continue;
+        targets[g] = resident(grp.keyframe_id, grp.points, grp.n, grp.stride_bytes);
+        for (const Candidate& c : grp.candidates) {
+          clouds.push_back(resident(c.keyframe_id, c.points, c.n, c.stride_bytes));
+          guesses.insert(guesses.end(), c.guess, c.guess + 16);
+        }
+      }
+      std::vector<hgs_result> out(clouds.size());
+      std::vector<int32_t> best32(groups.size(), -1);
+      check(eng, hgs_loop_match_groups(eng.h, targets.data(), groups.size(), offsets.data(), clouds.data(), guesses.data(), max_range, out.data(), best32.data()));
+      for (size_t g = 0; g < groups.size(); g++) {
+        (*records)[g].assign(out.begin() + offsets[g], out.begin() + offsets[g + 1]);
+        (*best)[g] = best32[g];
+      }
+    } catch (const std::exception& ex) {
+      last_error_ = std::string("engine 0: ") + ex.what() + "; ";
+      failed_engines_ = 1, ok = false;
+    }
+    try {
+      enforce_capacity(eng, tick);
+    } catch (const std::exception& ex) {
+      last_error_ += std::string("engine 0: ") + ex.what() + "; ";
+      failed_engines_ = 1, ok = false;
+    }
+    return ok;
+  }
   // empty after a clean match(); otherwise which engine failed and why (its candidates were left not converged)
   const std::string& last_error() const { return last_error_; }
   // engines of the last match() that had candidates / that failed: a caller that must not lose candidates silently (LoopDetector::matching)
@@ -190,6 +264,12 @@ private:
   size_t max_bytes_ = (size_t)16 << 30, max_keyframes_ = 0, used_engines_ = 0, failed_engines_ = 0;
   uint64_t tick_ = 0;
 
+  // Whether match_groups hands these groups to ONE hgs_loop_match_groups (otherwise: match() per group).  Measured shapes: DESIGN.md section 12.
+  static bool use_grouped_call(const std::vector<Group>& groups) {
+    size_t non_empty = 0;
+    for (const Group& g : groups) non_empty += g.candidates.empty() ? 0 : 1;
+    return non_empty >= 2;
+  }
   void drop(Engine& e, std::unordered_map<long, Resident>::iterator it) {
     e.bytes -= std::min(e.bytes, it->second.bytes);
     hgs_cloud_destroy(it->second.cloud);

@@ -134,6 +134,17 @@ void launch_icp_results(hipStream_t s, const IcpState* states, DevResult* out, i
 void launch_fitness(hipStream_t s, const CloudDesc* descs, TargetView tgt, const DevResult* poses, double max_range, double* partials, int max_blocks, int B,
                     int use_seed, int qpw);
 void launch_fitness_final(hipStream_t s, const CloudDesc* descs, const double* partials, int max_blocks, DevResult* out, int B, int tile_pts);
+// the point kernels with one target per problem, tviews[b] in HBM (hgs_loop_match_groups): their own instantiations of the same kernels (hgs_kernels.hip, problem_target)
+void launch_gicp_linearize(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states, GicpConsts c, double* partials, int max_blocks, int B,
+                           int qpw);
+void launch_gicp_error(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states, double* partials_err, int max_blocks, int B);
+void launch_gicp_linearize_round2(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states_in, GicpState* states_out, GicpConsts c, double* partials,
+                                  const double* partials_err, int max_blocks, int lin_blocks, int B, int qpw, Progress prog, DevResult* results, DevResult* early_out);
+void launch_gicp_error_round2(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states_in, GicpState* states_out, GicpConsts c, const double* partials,
+                              double* partials_err, int max_blocks, int err_blocks, int B, int lin_tile_points);
+void launch_icp_correspond(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const IcpState* states, IcpConsts c, double* partials, int max_blocks, int B);
+void launch_fitness(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const DevResult* poses, double max_range, double* partials, int max_blocks, int B,
+                    int use_seed, int qpw);
 }  // namespace hgs
 struct hgs_result;  // include/hgs_registration.h
 namespace hgs {

@@ -144,6 +144,7 @@ struct hgs_handle {
   DeviceBuffer staging, sort_keys[2], sort_vals[2], sort_tmp, descs, states, angles, partials, partials_err, results, guesses, done, misc;
   DeviceBuffer lane_partials[7], lane_partials_err[7];
   DeviceBuffer ndt_accum;  // NdtAccum per problem of the running NDT batch
+  DeviceBuffer group_tviews, group_corr;  // hgs_loop_match_groups: one TargetView and one correspondence scratch per problem (run_group_batch)
   hgs::Comm* comm = nullptr;            // hgs_comm_init: the ranks of a sharded loop-closure batch
   DeviceBuffer comm_send, comm_recv, comm_ids;
   DeviceBuffer pf_ukeys;         // prefilter: the voxels' keys in output order (k_pf_grid_radius_flags)
@@ -412,9 +413,10 @@ CloudDesc resident_desc(const hgs_cloud* c) {
   return d;
 }
 
-int upload_descs(hgs_handle* h, const std::vector<hgs_cloud*>& clouds, bool with_sort_offsets, const CloudDesc** dev, size_t* total_n) {
+// corr_of: a correspondence scratch per entry instead of the clouds' own (run_group_batch: one cloud may be the source of several problems of a batch)
+int upload_descs(hgs_handle* h, const std::vector<hgs_cloud*>& clouds, bool with_sort_offsets, const CloudDesc** dev, size_t* total_n, int* const* corr_of = nullptr) {
   const size_t B = clouds.size();
-  if (B == 1 && clouds[0]->dev_desc && h->resident_descs) {  // one cloud: its resident descriptor, no copy
+  if (B == 1 && clouds[0]->dev_desc && h->resident_descs && !corr_of) {  // one cloud: its resident descriptor, no copy
     if (total_n) *total_n = clouds[0]->n_input;
     *dev = clouds[0]->dev_desc;
     return HGS_OK;
@@ -428,6 +430,7 @@ int upload_descs(hgs_handle* h, const std::vector<hgs_cloud*>& clouds, bool with
   for (size_t i = 0; i < B; i++) {
     hd[i] = clouds[i]->desc;
     hd[i].sort_off = with_sort_offsets ? (int)off : 0;
+    if (corr_of) hd[i].corr = corr_of[i];
     off += clouds[i]->n_input;
   }
   if (total_n) *total_n = off;
@@ -851,11 +854,20 @@ struct BatchShape {
   int lin_qpw, lin_tile, lin_blocks;  // ... whose k_gicp_linearize<true> may run shorter packets
   int max_blocks, err_blocks;         // rows of the partial-sum buffers / blocks of the 256-point kernels, per problem
   const CloudDesc* d_descs;           // the sources' descriptors on the device
+  const TargetView* d_tviews;         // one target per problem, on the device (run_group_batch); null: every problem against the handle's target
 };
 
+// launch(target): with the lane's slice of the per-problem views, or with the one view `tv` by value — the two families of instantiations of the point kernels
+template <typename F>
+void with_lane_target(const BatchShape& s, const BatchLane& L, const TargetView& tv, F&& launch) {
+  if (s.d_tviews) launch(s.d_tviews + L.b0);
+  else launch(tv);
+}
+
 // lm_rounds: the batch iterates (run_batch); false: a fitness pass alone (run_fitness), which has no two-launch rounds to size for
-int batch_shape(hgs_handle* h, const std::vector<hgs_cloud*>& sources, bool lm_rounds, BatchShape* out) {
+int batch_shape(hgs_handle* h, const std::vector<hgs_cloud*>& sources, bool lm_rounds, BatchShape* out, int* const* corr_of = nullptr) {
   BatchShape& s = *out;
+  s.d_tviews = nullptr;
   s.B = (int)sources.size();
   s.max_n = 0;
   for (hgs_cloud* c : sources) s.max_n = std::max(s.max_n, (int)c->n_input);
@@ -878,7 +890,7 @@ int batch_shape(hgs_handle* h, const std::vector<hgs_cloud*>& sources, bool lm_r
   s.lin_blocks = std::max(1, (max_n + s.lin_tile - 1) / s.lin_tile);
   s.max_blocks = std::max(1, s.lin_qpw < 64 ? (max_n + 63) / 64 : (max_n + s.nn_tile - 1) / s.nn_tile);  // >= the tile (row) count of every kernel of the loop
   s.err_blocks = std::max(1, (max_n + kBlock - 1) / kBlock);
-  return upload_descs(h, sources, false, &s.d_descs, nullptr);
+  return upload_descs(h, sources, false, &s.d_descs, nullptr, corr_of);
 }
 
 // getFitnessScore of one lane's problems at the poses stored in h->results (exact 1-NN of every transformed source point in the target).
@@ -887,7 +899,8 @@ bool corr_seeds_fitness(int method) { return method == HGS_FAST_GICP || method =
 void lane_fitness(hgs_handle* h, BatchLane& L, const BatchShape& s, double max_range, bool corr_seeds) {
   StageTimer tm(h, HGS_STAGE_FITNESS);
   DevResult* res = h->results.as<DevResult>() + L.b0;
-  launch_fitness(L.stream, s.d_descs + L.b0, target_view(h->target), res, max_range, L.partials_err, s.max_blocks, L.B, corr_seeds ? 1 : 0, s.qpw);
+  with_lane_target(s, L, s.d_tviews ? TargetView{} : target_view(h->target),
+                   [&](auto tgt) { launch_fitness(L.stream, s.d_descs + L.b0, tgt, res, max_range, L.partials_err, s.max_blocks, L.B, corr_seeds ? 1 : 0, s.qpw); });
   launch_fitness_final(L.stream, s.d_descs + L.b0, L.partials_err, s.max_blocks, res, L.B, s.nn_tile);
 }
 // behind a lane's result kernel: the fitness pass of a batch that asked for one (FAST_GICP and ICP start it from the final correspondences)
@@ -914,7 +927,7 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
   HGS_HIP(h, h->states.reserve((size_t)B * sizeof(GicpState) * (round2 ? 2 : 1)));
   GicpState* st = h->states.as<GicpState>();
   GicpState* st_other = st + B;
-  const TargetView tv = target_view(tgt);
+  const TargetView tv = s.d_tviews ? TargetView{} : target_view(tgt);  // (run_group_batch: the views are on the device, the handle's target plays no part)
   const NdtTargetView vtv = voxel ? vgicp_target_view(tgt) : NdtTargetView{};
   const long max_rounds = (long)std::max(1, c.max_iterations) * std::max(1, c.lm_max_iterations) + 2 + (round2 ? 1 : 0);  // (round2: a round's accept / reject runs in the next round's first kernel)
   std::vector<BatchLane> lanes;
@@ -936,17 +949,21 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
     if (round2) {
       {
         StageTimer tm(h, HGS_STAGE_LINEARIZE);
-        launch_gicp_linearize_round2(L.stream, dd, tv, ls, st_other + L.b0, c, L.partials, L.partials_err, max_blocks, s.lin_blocks, L.B, s.lin_qpw, L.prog,
-                                     h->results.as<DevResult>() + L.b0, early_out);
+        with_lane_target(s, L, tv, [&](auto t) {
+          launch_gicp_linearize_round2(L.stream, dd, t, ls, st_other + L.b0, c, L.partials, L.partials_err, max_blocks, s.lin_blocks, L.B, s.lin_qpw, L.prog,
+                                       h->results.as<DevResult>() + L.b0, early_out);
+        });
       }
       StageTimer tm(h, HGS_STAGE_ERROR);
-      launch_gicp_error_round2(L.stream, dd, tv, st_other + L.b0, ls, c, L.partials, L.partials_err, max_blocks, s.err_blocks, L.B, s.lin_tile);
+      with_lane_target(s, L, tv, [&](auto t) {
+        launch_gicp_error_round2(L.stream, dd, t, st_other + L.b0, ls, c, L.partials, L.partials_err, max_blocks, s.err_blocks, L.B, s.lin_tile);
+      });
       return;
     }
     {
       StageTimer tm(h, HGS_STAGE_LINEARIZE);
       if (voxel) launch_vgicp_linearize(L.stream, dd, vtv, ls, vc, L.partials, max_blocks, L.B);
-      else launch_gicp_linearize(L.stream, dd, tv, ls, c, L.partials, max_blocks, L.B, s.qpw);
+      else with_lane_target(s, L, tv, [&](auto t) { launch_gicp_linearize(L.stream, dd, t, ls, c, L.partials, max_blocks, L.B, s.qpw); });
     }
     {
       StageTimer tm(h, HGS_STAGE_SOLVE);
@@ -955,7 +972,7 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
     {
       StageTimer tm(h, HGS_STAGE_ERROR);
       if (voxel) launch_vgicp_error(L.stream, dd, vtv, ls, vc, L.partials_err, max_blocks, L.B);
-      else launch_gicp_error(L.stream, dd, tv, ls, L.partials_err, max_blocks, L.B);
+      else with_lane_target(s, L, tv, [&](auto t) { launch_gicp_error(L.stream, dd, t, ls, L.partials_err, max_blocks, L.B); });
     }
     {
       StageTimer tm(h, HGS_STAGE_SOLVE);
@@ -978,7 +995,7 @@ int run_icp_rounds(hgs_handle* h, const BatchShape& s, const double* fit_max_ran
   const IcpConsts c = icp_consts(h->prm);
   HGS_HIP(h, h->states.reserve((size_t)B * sizeof(IcpState)));
   IcpState* st = h->states.as<IcpState>();
-  const TargetView tv = target_view(h->target);
+  const TargetView tv = s.d_tviews ? TargetView{} : target_view(h->target);
   const long max_rounds = (long)std::max(0, c.max_iterations) + 2;
   std::vector<BatchLane> lanes;
   HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccIcp * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
@@ -990,7 +1007,7 @@ int run_icp_rounds(hgs_handle* h, const BatchShape& s, const double* fit_max_ran
   drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
     {
       StageTimer tm(h, HGS_STAGE_LINEARIZE);
-      launch_icp_correspond(L.stream, s.d_descs + L.b0, tv, st + L.b0, c, L.partials, max_blocks, L.B);
+      with_lane_target(s, L, tv, [&](auto t) { launch_icp_correspond(L.stream, s.d_descs + L.b0, t, st + L.b0, c, L.partials, max_blocks, L.B); });
     }
     StageTimer tm(h, HGS_STAGE_SOLVE);
     launch_icp_solve(L.stream, s.d_descs + L.b0, st + L.b0, c, L.partials, max_blocks, L.B, L.prog);
@@ -1128,6 +1145,49 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
   if (gicp) HGS_TRY(run_gicp_rounds(h, s, guesses_host, guess_in_args, fit_max_range));
   else if (method == HGS_ICP) HGS_TRY(run_icp_rounds(h, s, fit_max_range));
   else HGS_TRY(run_ndt_rounds(h, sources, s, fit_max_range));
+  HGS_HIP(h, hipGetLastError());
+  return HGS_OK;
+}
+
+// hgs_loop_match_groups: problem b registers sources[b] against targets[b] and runs getFitnessScore(max_range) behind it, all problems in ONE batch — the
+// lanes, the two-launch rounds and the packet tiers are chosen by batch_shape / open_lanes on the whole list as for a batch against one target.  What differs:
+//   * the target views sit in a device array, one per problem (the point kernels' const TargetView* instantiations read tviews[blockIdx.y]);
+//   * every problem has its own correspondence scratch (h->group_corr, through its descriptor) instead of the source cloud's corr[]: one keyframe is a
+//     candidate of several new keyframes.  The scratch starts at -1 like a cloud's corr[] behind its index build; the searches are exact and a seed only
+//     bounds the walk (k_gicp_linearize), so a record equals the one a batch against that target alone gives, bit for bit;
+//   * neither h->target nor h->source is read or written.
+// FAST_GICP and ICP only (the caller has checked): their targets are a search index (+ covariances), which every cloud of the union gets in one ensure_* pass.
+int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const std::vector<hgs_cloud*>& sources, const float* guesses_host, double max_range) {
+  const int B = (int)sources.size();
+  const int method = h->prm.method;
+  h->early_valid = false;
+  std::vector<hgs_cloud*> all(sources);
+  all.insert(all.end(), targets.begin(), targets.end());
+  if (method == HGS_FAST_GICP) HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
+  else HGS_TRY(ensure_index(h, all));
+  if (method != HGS_FAST_GICP)  // as run_batch: the fitness pass of a point without a correspondence starts from the target's seed grid
+    for (hgs_cloud* t : targets) HGS_TRY(ensure_seed_grid(h, t));
+  // the correspondence scratch of problem b: as many entries as the source's own corr[] (its padded point count), 256-byte aligned
+  std::vector<size_t> corr_off(B + 1, 0);
+  for (int b = 0; b < B; b++) corr_off[b + 1] = corr_off[b] + align_up((size_t)sources[b]->P * kLeaf, 64);
+  HGS_HIP(h, h->group_corr.reserve(std::max<size_t>(1, corr_off[B]) * sizeof(int)));
+  HGS_HIP(h, hipMemsetAsync(h->group_corr.p, 0xff, corr_off[B] * sizeof(int), h->stream));
+  std::vector<int*> corr_of(B);
+  for (int b = 0; b < B; b++) corr_of[b] = h->group_corr.as<int>() + corr_off[b];
+  std::vector<TargetView> views(B);
+  for (int b = 0; b < B; b++) views[b] = target_view(targets[b]);
+  HGS_HIP(h, h->group_tviews.reserve((size_t)B * sizeof(TargetView)));
+  HGS_HIP(h, h->up.upload(h->group_tviews.p, views.data(), (size_t)B * sizeof(TargetView), h->stream));
+  BatchShape s;
+  HGS_TRY(batch_shape(h, sources, true, &s, corr_of.data()));
+  s.d_tviews = h->group_tviews.as<TargetView>();
+  HGS_HIP(h, h->guesses.reserve((size_t)B * 16 * sizeof(float)));
+  HGS_HIP(h, h->up.upload(h->guesses.p, guesses_host, (size_t)B * 16 * sizeof(float), h->stream));
+  HGS_HIP(h, h->results.reserve((size_t)B * sizeof(DevResult)));
+  HGS_HIP(h, h->partials.reserve((size_t)B * s.max_blocks * kAccNdt * sizeof(double)));
+  HGS_HIP(h, h->partials_err.reserve((size_t)B * s.max_blocks * 2 * sizeof(double)));
+  if (method == HGS_FAST_GICP) HGS_TRY(run_gicp_rounds(h, s, guesses_host, false, &max_range));
+  else HGS_TRY(run_icp_rounds(h, s, &max_range));
   HGS_HIP(h, hipGetLastError());
   return HGS_OK;
 }
@@ -1646,6 +1706,57 @@ int hgs_loop_match_batch(hgs_handle* h, hgs_cloud* const* candidates, size_t n_c
   HGS_TRY(fetch_results(h, (int)n_candidates, r));
   for (size_t i = 0; i < n_candidates; i++) to_public(r[i], (int)i, true, &out[i]);
   if (best) HGS_TRY(hgs_select_best(out, n_candidates, best));
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+// LoopDetector::detect (loop_detector.hpp:57-68) calls matching once per new keyframe of a graph update; this is the candidates of ALL of them in one batch.
+int hgs_loop_match_groups(hgs_handle* h, hgs_cloud* const* targets, size_t n_groups, const size_t* group_offsets, hgs_cloud* const* candidates, const float* guesses,
+                          double max_range, hgs_result* out, int32_t* best) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (n_groups == 0) return HGS_OK;
+  if (!group_offsets || !targets || group_offsets[0] != 0) return HGS_ERR_INVALID_ARGUMENT;
+  for (size_t g = 0; g < n_groups; g++)
+    if (group_offsets[g + 1] < group_offsets[g]) {
+      h->err = "hgs_loop_match_groups: group_offsets must not decrease";
+      return HGS_ERR_INVALID_ARGUMENT;
+    }
+  const size_t n = group_offsets[n_groups];
+  if (n > (size_t)INT_MAX || (n > 0 && (!candidates || !guesses || !out))) return HGS_ERR_INVALID_ARGUMENT;
+  if (h->prm.method != HGS_FAST_GICP && h->prm.method != HGS_ICP) {
+    h->err = "hgs_loop_match_groups: FAST_GICP and ICP only (one hgs_loop_match_batch per target serves the other methods)";
+    return HGS_ERR_UNSUPPORTED;
+  }
+  std::vector<hgs_cloud*> tgt(n), src(candidates, candidates + n);
+  for (size_t g = 0; g < n_groups; g++) {
+    const size_t g0 = group_offsets[g], g1 = group_offsets[g + 1];
+    if (best) best[g] = -1;
+    if (g0 == g1) continue;  // (an empty group's target is not looked at)
+    if (!targets[g] || targets[g]->owner != h) return HGS_ERR_INVALID_ARGUMENT;
+    for (size_t i = g0; i < g1; i++) {
+      if (!src[i] || src[i]->owner != h) return HGS_ERR_INVALID_ARGUMENT;
+      tgt[i] = targets[g];
+    }
+    // as hgs_loop_match_batch: the candidates of ONE new keyframe are distinct keyframes (across groups a cloud may repeat)
+    std::vector<hgs_cloud*> sorted(src.begin() + g0, src.begin() + g1);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+      h->err = "hgs_loop_match_groups: the candidate clouds of one group must be distinct";
+      return HGS_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (n == 0) return HGS_OK;
+  HGS_TRY(set_device(h));
+  HGS_TRY(run_group_batch(h, tgt, src, guesses, max_range));
+  std::vector<DevResult> r;
+  HGS_TRY(fetch_results(h, (int)n, r));
+  for (size_t g = 0; g < n_groups; g++) {
+    const size_t g0 = group_offsets[g], g1 = group_offsets[g + 1];
+    for (size_t i = g0; i < g1; i++) to_public(r[i], (int)(i - g0), true, &out[i]);
+    if (best && g1 > g0) HGS_TRY(hgs_select_best(out + g0, g1 - g0, &best[g]));
+  }
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);

@@ -251,6 +251,29 @@ __device__ __forceinline__ BvhView view_of(const TargetView& t) {
   return v;
 }
 
+// The target of problem b of a point kernel (template parameter TGT of k_gicp_linearize / k_gicp_error / k_icp_correspond / k_fitness).  TargetView: the
+// launch's one target, by value in the kernel arguments (hgs_align, hgs_loop_match_batch).  const TargetView*: one view per problem in HBM
+// (hgs_loop_match_groups: LoopDetector::detect, loop_detector.hpp:57-68, hands over several new keyframes, each the target of its own candidates).  The
+// entry's address is block-uniform and the record is read once, in front of the kernel's first store: scalar loads, and the walk's view stays in scalar
+// registers as the by-value form's does.  Two instantiations, not a run-time branch in one (see k_gicp_linearize on what sharing a function does to the last bits).
+// A pointer in a kernel argument is known to the compiler as a global address; one read from a record in memory is not (see HGS_LOAD_GLOBAL_XYZ on
+// what flat loads cost the walk) — the view's pointers are declared global here, so both forms issue the same global / scalar loads.
+template <typename T>
+__device__ __forceinline__ const T* global_pointer(const T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (const T*)(const __attribute__((address_space(1))) T*)(unsigned long long)p;  // (through an integer: a plain cast there and back is folded away)
+#else
+  return p;
+#endif
+}
+__device__ __forceinline__ const TargetView& problem_target(const TargetView& t, int) { return t; }
+__device__ __forceinline__ TargetView problem_target(const TargetView* __restrict__ tviews, int b) {
+  TargetView t = global_pointer(tviews)[b];
+  t.nodes = global_pointer(t.nodes), t.pts = global_pointer(t.pts), t.lpts = global_pointer(t.lpts), t.cov = global_pointer(t.cov);
+  t.meta = global_pointer(t.meta), t.seed_tab = global_pointer(t.seed_tab);
+  return t;
+}
+
 // ------------------------------------------------------------------------------------------------ upload
 // (round 5) the packing kernel of a new cloud also resets the cloud's meta record — nvalid and the bounding box k_bbox_count accumulates into with atomics
 // right behind it in the stream: one dispatch less per uploaded sweep than the separate k_meta_init
@@ -938,11 +961,12 @@ __device__ __forceinline__ void gicp_wave_row(const GicpPointResidual& r, const 
 // SHORT (with ROUND2 only): the short-packet form, below.  Its own instantiation and not a branch: with both forms of the per-point arithmetic in one function
 // the compiler shared subexpressions between them and contracted the 64-query form's multiplies and adds differently from k_gicp_linearize<false>'s
 // (measured: the last bits of the pose moved; profiles/r06_ab13_short_packets.log).
-template <bool ROUND2, bool SHORT = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ROUND2 ? 4 : HGS_LINEARIZE_WAVES))) void k_gicp_linearize(const CloudDesc* descs, TargetView tgt, const GicpState* states, GicpConsts c,
+template <bool ROUND2, bool SHORT = false, typename TGT = TargetView>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ROUND2 ? 4 : HGS_LINEARIZE_WAVES))) void k_gicp_linearize(const CloudDesc* descs, TGT tgt_arg, const GicpState* states, GicpConsts c,
                                                            double* __restrict__ partials, int max_blocks, int qpw, GicpState* states_out,
                                                            const double* __restrict__ partials_err, Progress prog, DevResult* results, DevResult* early_out) {
   const int b = blockIdx.y;
+  const TargetView& tgt = problem_target(tgt_arg, b);
   __shared__ GicpState st2;                         // ROUND2: this block's copy of the problem's state
   __shared__ double ws2[kGicpControlWorkspace];
   if constexpr (!ROUND2) {
@@ -1071,6 +1095,19 @@ void launch_gicp_linearize_round2(hipStream_t s, const CloudDesc* descs, TargetV
   else
     hipLaunchKernelGGL((k_gicp_linearize<true, false>), dim3(HGS_GRID_X(lin_blocks), B), dim3(kBlock), 0, s, descs, tgt, states_in, c, partials, max_blocks, qpw, states_out, partials_err, prog, results, early_out);
 }
+// ... the same launches with one target per problem (tviews[b]: hgs_loop_match_groups)
+void launch_gicp_linearize(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states, GicpConsts c, double* partials,
+                           int max_blocks, int B, int qpw) {
+  hipLaunchKernelGGL((k_gicp_linearize<false, false, const TargetView*>), dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tviews, states, c, partials, max_blocks, qpw,
+                     (GicpState*)nullptr, (const double*)nullptr, Progress{}, (DevResult*)nullptr, (DevResult*)nullptr);
+}
+void launch_gicp_linearize_round2(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states_in, GicpState* states_out, GicpConsts c, double* partials,
+                                  const double* partials_err, int max_blocks, int lin_blocks, int B, int qpw, Progress prog, DevResult* results, DevResult* early_out) {
+  if (qpw < 64)
+    hipLaunchKernelGGL((k_gicp_linearize<true, true, const TargetView*>), dim3(HGS_GRID_X(lin_blocks), B), dim3(kBlock), 0, s, descs, tviews, states_in, c, partials, max_blocks, qpw, states_out, partials_err, prog, results, early_out);
+  else
+    hipLaunchKernelGGL((k_gicp_linearize<true, false, const TargetView*>), dim3(HGS_GRID_X(lin_blocks), B), dim3(kBlock), 0, s, descs, tviews, states_in, c, partials, max_blocks, qpw, states_out, partials_err, prog, results, early_out);
+}
 
 // The LM control step behind a linearisation, run by a whole 256-thread block: fixed-order tile reduction, then ONE lane factorises and steps.  The
 // control step is a chain of dependent loads and stores on the problem's state and on the factorisation's pivoted arrays: both live in LDS for its
@@ -1106,10 +1143,11 @@ void launch_gicp_solve(hipStream_t s, const CloudDesc* descs, GicpState* states,
 // compute_error(xi): same correspondences, Mahalanobis matrices of the linearisation pose x0, residuals at xi.
 // ROUND2 (k_gicp_error<true>): the LM solve of the linearisation the previous k_gicp_linearize<true> made (gicp_solve_block's arithmetic, in its order)
 // runs first, in every block; `partials` / lin_tile_points: that kernel's tile partials and tiling.
-template <bool ROUND2>
-__global__ __launch_bounds__(kBlock) void k_gicp_error(const CloudDesc* descs, TargetView tgt, const GicpState* states, double* __restrict__ partials_err,
+template <bool ROUND2, typename TGT = TargetView>
+__global__ __launch_bounds__(kBlock) void k_gicp_error(const CloudDesc* descs, TGT tgt_arg, const GicpState* states, double* __restrict__ partials_err,
                                                        int max_blocks, GicpConsts c, GicpState* states_out, const double* __restrict__ partials, int lin_tile_points) {
   const int b = blockIdx.y;
+  const TargetView& tgt = problem_target(tgt_arg, b);
   __shared__ GicpState st2;
   __shared__ double ws2[kGicpControlWorkspace];
   __shared__ double acc2[kAcc];
@@ -1158,6 +1196,14 @@ void launch_gicp_error(hipStream_t s, const CloudDesc* descs, TargetView tgt, co
 void launch_gicp_error_round2(hipStream_t s, const CloudDesc* descs, TargetView tgt, const GicpState* states_in, GicpState* states_out, GicpConsts c, const double* partials,
                               double* partials_err, int max_blocks, int err_blocks, int B, int lin_tile_points) {
   hipLaunchKernelGGL(k_gicp_error<true>, dim3(err_blocks, B), dim3(kBlock), 0, s, descs, tgt, states_in, partials_err, max_blocks, c, states_out, partials, lin_tile_points);
+}
+void launch_gicp_error(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states, double* partials_err, int max_blocks, int B) {
+  hipLaunchKernelGGL((k_gicp_error<false, const TargetView*>), dim3(max_blocks, B), dim3(kBlock), 0, s, descs, tviews, states, partials_err, max_blocks, GicpConsts{}, (GicpState*)nullptr,
+                     (const double*)nullptr, 0);
+}
+void launch_gicp_error_round2(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const GicpState* states_in, GicpState* states_out, GicpConsts c, const double* partials,
+                              double* partials_err, int max_blocks, int err_blocks, int B, int lin_tile_points) {
+  hipLaunchKernelGGL((k_gicp_error<true, const TargetView*>), dim3(err_blocks, B), dim3(kBlock), 0, s, descs, tviews, states_in, partials_err, max_blocks, c, states_out, partials, lin_tile_points);
 }
 
 // The LM accept / reject step behind compute_error, run by ONE wave (the first 64 threads of the calling block; the others only pass the barriers):
@@ -1226,10 +1272,11 @@ void launch_icp_init(hipStream_t s, IcpState* states, const float* guesses, int 
 // frame must find this very point as its exact 1-NN in the source's own index, again within max_corr^2.  The 17 sums of the kept pairs
 // (hgs_icp.h kAccIcp) go through the wave sums and last_wave_stores into one partial row per 256-point tile; corr[] keeps the
 // correspondence (sorted target position or -1) as the next pass's seed and for the fitness pass.
-template <bool RECIPROCAL>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_LINEARIZE_WAVES))) void k_icp_correspond(const CloudDesc* descs, TargetView tgt, const IcpState* states,
+template <bool RECIPROCAL, typename TGT = TargetView>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_LINEARIZE_WAVES))) void k_icp_correspond(const CloudDesc* descs, TGT tgt_arg, const IcpState* states,
                                                                                                        IcpConsts c, double* __restrict__ partials, int max_blocks) {
   const int b = blockIdx.y;
+  const TargetView& tgt = problem_target(tgt_arg, b);
   if (states[b].phase != ICP_RUN) return;
   const CloudDesc d = descs[b];
   const int n = d.meta->nvalid;
@@ -1288,6 +1335,10 @@ void launch_icp_correspond(hipStream_t s, const CloudDesc* descs, TargetView tgt
   if (c.reciprocal) hipLaunchKernelGGL(k_icp_correspond<true>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, states, c, partials, max_blocks);
   else hipLaunchKernelGGL(k_icp_correspond<false>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, states, c, partials, max_blocks);
 }
+void launch_icp_correspond(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const IcpState* states, IcpConsts c, double* partials, int max_blocks, int B) {
+  if (c.reciprocal) hipLaunchKernelGGL((k_icp_correspond<true, const TargetView*>), dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tviews, states, c, partials, max_blocks);
+  else hipLaunchKernelGGL((k_icp_correspond<false, const TargetView*>), dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tviews, states, c, partials, max_blocks);
+}
 
 // One wave per problem: the tile partials added in a fixed order (lane l takes tiles l, l + 64, ...; then the wave sum) — the result
 // depends on the problem's own points only, not on lanes, batch or launch shape — then the Umeyama step and the convergence tests
@@ -1339,9 +1390,11 @@ void launch_icp_results(hipStream_t s, const IcpState* states, DevResult* out, i
 // ------------------------------------------------------------------------------------------------ fitness / NN queries
 // getFitnessScore: per source point exact (unbounded) 1-NN in the target; sum d2 over d2 <= max_range.
 // Algorithmic bytes per source point: 16 + 16 = 32.  Only the distance is needed: the quad walk runs without leaf / tie tracking.
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_FITNESS_WAVES))) void k_fitness(const CloudDesc* descs, TargetView tgt, const DevResult* poses, double max_range,
+template <typename TGT = TargetView>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_FITNESS_WAVES))) void k_fitness(const CloudDesc* descs, TGT tgt_arg, const DevResult* poses, double max_range,
                                                     double* __restrict__ partials, int max_blocks, int use_seed, int qpw) {
   const int b = blockIdx.y;
+  const TargetView& tgt = problem_target(tgt_arg, b);
   const CloudDesc d = descs[b];
   const int n = d.meta->nvalid;
   const int tile_pts = (kBlock / 64) * qpw * kNW;
@@ -1388,7 +1441,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HGS_FITN
 }
 void launch_fitness(hipStream_t s, const CloudDesc* descs, TargetView tgt, const DevResult* poses, double max_range, double* partials, int max_blocks,
                     int B, int use_seed, int qpw) {
-  hipLaunchKernelGGL(k_fitness, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, poses, max_range, partials, max_blocks, use_seed, qpw);
+  hipLaunchKernelGGL(k_fitness<TargetView>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tgt, poses, max_range, partials, max_blocks, use_seed, qpw);
+}
+void launch_fitness(hipStream_t s, const CloudDesc* descs, const TargetView* tviews, const DevResult* poses, double max_range, double* partials, int max_blocks,
+                    int B, int use_seed, int qpw) {
+  hipLaunchKernelGGL(k_fitness<const TargetView*>, dim3(HGS_GRID_X(max_blocks), B), dim3(kBlock), 0, s, descs, tviews, poses, max_range, partials, max_blocks, use_seed, qpw);
 }
 __global__ __launch_bounds__(64) void k_fitness_final(const CloudDesc* descs, const double* __restrict__ partials, int max_blocks, DevResult* out, int tile_pts) {
   const int b = blockIdx.x;

@@ -7,6 +7,9 @@ Semantics kept from the reference:
   * per candidate: align + getFitnessScore(fitness_score_max_range) (:143-146);
   * selection: iterate in candidate order, skip if !converged or score > best_score, ties replace (:147-153);
   * reject if best_score > fitness_score_thresh (:160), else last_edge_accum_distance = new_keyframe.accum_distance (:168).
+
+reg_hip_batch_new_keyframes (default false): detect() hands the candidates of ALL new keyframes of an update (loop_detector.hpp:57-68) to the
+device in one grouped call and replays the reference's order on the host (LoopDetector._detect_grouped).
 """
 from __future__ import annotations
 
@@ -81,8 +84,16 @@ class LoopDetector:
         self.registration = registration or select_registration_method(pnh, device_id)  # :47
         self.last_edge_accum_distance = 0.0
         self.shard = shard  # optional hdl_graph_slam_amd.distributed.CandidateShard (multi-GPU)
+        self.batch_new_keyframes = bool(get("reg_hip_batch_new_keyframes", False))
+        self.last_detect_grouped = False   # whether the last detect() went through the grouped call
 
     def detect(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> List[Loop]:
+        self.last_detect_grouped = False
+        if self.batch_new_keyframes and self.shard is None:
+            loops = self._detect_grouped(keyframes, new_keyframes)
+            if loops is not None:
+                self.last_detect_grouped = True
+                return loops
         loops = []
         for nk in new_keyframes:
             loop = self.matching(self.find_candidates(keyframes, nk), nk)
@@ -90,9 +101,54 @@ class LoopDetector:
                 loops.append(loop)
         return loops
 
+    def _detect_grouped(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> Optional[List[Loop]]:
+        """detect() with one device call for the whole update.  The only state the sequential loop carries from one new keyframe to the next
+        is last_edge_accum_distance, which matching() only ever RAISES (to the accepted keyframe's accum_distance, :168; keyframes arrive in
+        order of accumulated distance), and which only enters through the last-edge gate (:83-86):
+          1. a new keyframe that fails the gate against the value at entry fails it against every later value: dropped;
+          2. the others get their candidates by the two state-free tests (:90-106) and are matched speculatively, all in one grouped call;
+          3. the host replays the loop in order: gate against the running value (a keyframe that now fails is skipped, its records are
+             discarded — the sequential loop would not have matched it), selection and threshold (:147-168), raise the value on acceptance.
+        A record depends on its own target, source and guess only (bitwise), so what the replay reads is what matching() would have read.
+        Returns None when the engine does not serve the grouped call (NDT_OMP, FAST_VGICP): the caller runs the sequential loop."""
+        entry = self.last_edge_accum_distance
+        groups = []
+        for nk in new_keyframes:
+            if nk.accum_distance - entry < self.distance_from_last_edge_thresh:
+                continue
+            cands = self._candidates_by_distance(keyframes, nk)
+            if cands:
+                groups.append((nk, cands))
+        if not groups:
+            return []
+        reg = self.registration
+        guesses = [[loop_guess(nk.estimate, c.estimate) for c in cands] for nk, cands in groups]
+        records, best, rc = reg.loop_match_groups([self._resident(nk) for nk, _ in groups], [[self._resident(c) for c in cands] for _, cands in groups],
+                                                  guesses, self.fitness_score_max_range, return_status=True)
+        if rc == L.HGS_ERR_UNSUPPORTED:
+            return None
+        reg._check(rc)
+        loops, first = [], 0
+        for g, (nk, cands) in enumerate(groups):
+            rec = records[first:first + len(cands)]
+            first += len(cands)
+            if nk.accum_distance - self.last_edge_accum_distance < self.distance_from_last_edge_thresh:
+                continue                                                                  # gated by a loop accepted earlier in this update
+            self.last_records = rec
+            b = int(best[g])
+            if b < 0 or float(rec["fitness_score"][b]) > self.fitness_score_thresh:      # :160-163
+                continue
+            self.last_edge_accum_distance = nk.accum_distance                             # :168
+            loops.append(Loop(nk, cands[b], np.array(rec["final_transformation"][b], np.float32).reshape(4, 4).T.copy()))
+        return loops
+
     def find_candidates(self, keyframes: Sequence[KeyFrame], new_keyframe: KeyFrame) -> List[KeyFrame]:
         if new_keyframe.accum_distance - self.last_edge_accum_distance < self.distance_from_last_edge_thresh:
             return []
+        return self._candidates_by_distance(keyframes, new_keyframe)
+
+    def _candidates_by_distance(self, keyframes: Sequence[KeyFrame], new_keyframe: KeyFrame) -> List[KeyFrame]:
+        """The two tests of find_candidates that read no detector state (loop_detector.hpp:90-106)."""
         out = []
         p2 = np.asarray(new_keyframe.estimate)[:2, 3]
         for k in keyframes:

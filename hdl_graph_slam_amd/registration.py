@@ -214,6 +214,28 @@ class RegistrationHIP:
                                                  C.byref(best)))
         return out, best.value
 
+    def loop_match_groups(self, targets, groups, guesses, max_range: float = L.DBL_MAX, return_status: bool = False):
+        """The candidates of several new keyframes in one batch (hgs_loop_match_groups; LoopDetector::detect, loop_detector.hpp:57-68):
+        groups[g] — a list of DeviceClouds — is registered against targets[g], guesses[g][i] is the guess of groups[g][i].  Returns
+        (records of all candidates, group after group; best index per group, -1 = none).  The engine's own target and source stay as they are.
+        return_status: do not raise but return (records, best, status) — HGS_ERR_UNSUPPORTED tells the caller to run one batch per target."""
+        ng = len(groups)
+        offsets = np.zeros(ng + 1, np.uintp)
+        offsets[1:] = np.cumsum([len(g) for g in groups])
+        n = int(offsets[ng])
+        tptr = (C.c_void_p * max(ng, 1))(*[(t._h if t is not None else None) for t in targets])
+        cptr = (C.c_void_p * max(n, 1))(*[c._h for g in groups for c in g])
+        flat = [L.colmajor16(T) for gg in guesses for T in gg]
+        g = np.ascontiguousarray(np.stack(flat) if flat else np.zeros((0, 16), np.float32))
+        out = np.zeros(n, dtype=L.RESULT_DTYPE)
+        best = np.full(ng, -1, np.int32)
+        rc = L.lib().hgs_loop_match_groups(self._h, tptr, ng, offsets.ctypes.data_as(C.c_void_p), cptr, g.ctypes.data_as(C.c_void_p), float(max_range),
+                                           out.ctypes.data_as(C.c_void_p), best.ctypes.data_as(C.c_void_p))
+        if return_status:
+            return out, best, rc
+        self._check(rc)
+        return out, best
+
     # ---- sharded batch: one process per GPU, records all-gathered by RCCL on the engine's stream (include/hgs_registration.h)
     @staticmethod
     def comm_unique_id() -> bytes:

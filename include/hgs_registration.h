@@ -169,6 +169,20 @@ int hgs_nn_target(hgs_handle* h, const float* q_xyz, size_t nq, size_t stride_by
  * the LAST minimal candidate wins), or -1 if none. */
 int hgs_loop_match_batch(hgs_handle* h, hgs_cloud* const* candidates, size_t n_candidates, const float* guesses /* 16*n */,
                          double max_range, hgs_result* out, int32_t* best);
+/* The candidates of SEVERAL new keyframes in one batch: LoopDetector::detect (loop_detector.hpp:57-68) calls matching once per new keyframe of a
+ * graph update — up to max_keyframes_per_update of them — and every call is a short launch chain that does not fill the device.  Group g registers
+ * candidates[group_offsets[g] .. group_offsets[g + 1]) against targets[g], each followed by getFitnessScore(max_range); out[i].candidate_id is the
+ * index inside the group and best[g] what hgs_select_best gives over the group's records (-1: none, also for an empty group).  Every record is
+ * bitwise what hgs_set_target_cloud(targets[g]) + hgs_loop_match_batch over that group alone returns.  The handle's own target and source
+ * (hgs_set_*) are neither used nor changed.  A group may be empty (its target may then be NULL); n_groups == 0 returns HGS_OK.  Inside one group
+ * the candidate clouds must be distinct; across groups a cloud may repeat, and a cloud may be the target of one group and a candidate of another.
+ * HGS_FAST_GICP and HGS_ICP; HGS_NDT_OMP and HGS_FAST_VGICP return HGS_ERR_UNSUPPORTED (call hgs_loop_match_batch per target). */
+int hgs_loop_match_groups(hgs_handle* h, hgs_cloud* const* targets, size_t n_groups,
+                          const size_t* group_offsets /* n_groups + 1, non-decreasing, [0] = 0 */,
+                          hgs_cloud* const* candidates /* group_offsets[n_groups] */,
+                          const float* guesses /* 16 floats per candidate, column-major */,
+                          double max_range, hgs_result* out /* one per candidate */,
+                          int32_t* best /* n_groups entries, -1 = none; NULL ok */);
 /* Pure host helper: the sequential selection rule above applied to an arbitrary record list (used after the
  * multi-GPU all-gather of per-candidate records). */
 int hgs_select_best(const hgs_result* records, size_t n, int32_t* best);
