@@ -109,7 +109,7 @@ EXPORTS = [
     "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_cloud_download", "hgs_map_cloud_generate",
     "hgs_floor_params_default", "hgs_detect_floor", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
-    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
+    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_vgicp_voxels", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
 ]
 
 _lib = None
@@ -170,6 +170,7 @@ def lib():
     L.hgs_debug_icp_correspond.argtypes = [vp, vp, vp, vp]
     L.hgs_debug_icp_step.argtypes = [vp, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
     L.hgs_debug_ndt_cells.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+    L.hgs_debug_vgicp_voxels.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     L.hgs_debug_ndt_derivatives.argtypes = [vp, vp, vp, vp, vp]
     L.hgs_debug_merge_shard_records.argtypes = [vp, vp, C.c_int32, C.c_size_t, C.c_size_t, vp, vp]
     _lib = L

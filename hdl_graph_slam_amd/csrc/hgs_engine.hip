@@ -81,6 +81,8 @@ struct hgs_cloud {
   bool has_vg = false;
   double vg_resolution = 0;
   int vg_cov_k = 0;
+  long long vg_span[3] = {0, 0, 0};  // cells per axis of the map's bounding box; their product above INT_MAX: no map (ensure_vgicp_target)
+  bool vg_too_large = false;
   VoxelTable vg;
   // seed grid (target role of the 1-NN kernels: seed_grid_lookup, hgs_kernels.hip)
   bool has_seed = false;
@@ -624,12 +626,25 @@ int ensure_ndt_target(hgs_handle* h, hgs_cloud* c) {
   return HGS_OK;
 }
 
+// A target whose voxel bounding box holds more cells than a 32-bit linear key addresses has no map (k_vgicp_grid_params raised vg_error and every
+// key is the sentinel): registering against it would "converge" at the guess without a single correspondence, so the entry points refuse it.
+int vgicp_grid_too_large(hgs_handle* h, const hgs_cloud* c) {
+  char msg[256];
+  snprintf(msg, sizeof(msg),
+           "FAST_VGICP: the target's voxel grid spans %lld x %lld x %lld cells at resolution %g, more than the 2147483647 a linear voxel key addresses "
+           "(a far stray point in the target?)",
+           c->vg_span[0], c->vg_span[1], c->vg_span[2], c->vg_resolution);
+  h->err = msg;
+  return HGS_ERR_UNSUPPORTED;
+}
+
 // FastVGICP's GaussianVoxelMap of the target (needs the target's kNN covariances first).  Upstream rebuilds it at
-// the start of every align(); the result only depends on (target, resolution, k), so it is cached on the cloud.
+// the start of every align(); the result only depends on (target, resolution, k), so it is cached on the cloud — and with it whether the grid
+// was too large: the flag comes back once per build (one small copy and the wait for it, like the prefilter's), never per align.
 int ensure_vgicp_target(hgs_handle* h, hgs_cloud* c) {
   const double res = h->prm.resolution;
   const int k = h->prm.correspondence_randomness;
-  if (c->has_vg && c->vg_resolution == res && c->vg_cov_k == cov_cache_key(h, k)) return HGS_OK;
+  if (c->has_vg && c->vg_resolution == res && c->vg_cov_k == cov_cache_key(h, k)) return c->vg_too_large ? vgicp_grid_too_large(h, c) : HGS_OK;
   StageTimer tm(h, HGS_STAGE_VOXELIZE);
   const int max_cells = (int)c->n_input + 1;
   const int cap = next_pow2(std::max<int>(64, 2 * max_cells));
@@ -639,10 +654,16 @@ int ensure_vgicp_target(hgs_handle* h, hgs_cloud* c) {
       [&](unsigned long long* keys, unsigned* vals) { launch_vgicp_cell_keys(h->stream, c->desc, res, keys, vals); },
       [&](unsigned long long* keys, unsigned* vals) { launch_vgicp_build_cells(h->stream, c->desc, keys, vals, t.hash_keys, t.hash_vals, cap - 1, t.cells); }));
   HGS_HIP(h, hipGetLastError());
+  HGS_HIP(h, h->h_small.reserve(sizeof(CloudMeta)));
+  const CloudMeta* hm = h->h_small.as<CloudMeta>();
+  HGS_HIP(h, hipMemcpyAsync(h->h_small.p, c->desc.meta, sizeof(CloudMeta), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int d = 0; d < 3; d++) c->vg_span[d] = (long long)hm->vg_max_b[d] - hm->vg_min_b[d] + 1;
+  c->vg_too_large = hm->vg_error != 0;
   c->has_vg = true;
   c->vg_resolution = res;
   c->vg_cov_k = cov_cache_key(h, k);
-  return HGS_OK;
+  return c->vg_too_large ? vgicp_grid_too_large(h, c) : HGS_OK;
 }
 
 // inv_leaf: 1 / resolution for NDT's tables, 0 for VGICP's (its kernels take the resolution from VgicpConsts)
@@ -2889,6 +2910,46 @@ int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3
     if (mean3) mean3[3 * i] = cells[i].mean[0], mean3[3 * i + 1] = cells[i].mean[1], mean3[3 * i + 2] = cells[i].mean[2];
     if (icov6) {
       float* o = icov6 + 6 * i;
+      o[0] = cells[i].v0.x, o[1] = cells[i].v0.y, o[2] = cells[i].v0.z, o[3] = cells[i].v0.w, o[4] = cells[i].v1.x, o[5] = cells[i].v1.y;
+    }
+    if (npts) npts[i] = (int)cells[i].v1.z;
+  }
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_vgicp_voxels(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* cov6, int32_t* npts, int32_t* n_cells) try {
+  ApiLock lock(h);
+  if (!h || !n_cells) return HGS_ERR_INVALID_ARGUMENT;
+  if (h->prm.method != HGS_FAST_VGICP) return HGS_ERR_UNSUPPORTED;
+  if (!h->target) return HGS_ERR_NO_TARGET;
+  HGS_TRY(set_device(h));
+  hgs_cloud* t = h->target;
+  std::vector<hgs_cloud*> all{t};
+  HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
+  HGS_TRY(ensure_vgicp_target(h, t));
+  CloudMeta meta;
+  HGS_HIP(h, hipMemcpyAsync(&meta, t->desc.meta, sizeof(CloudMeta), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  *n_cells = meta.vg_ncells;
+  const int n = std::min<int>(meta.vg_ncells, cap);
+  if (n <= 0) return HGS_OK;
+  std::vector<NdtCellRec> cells(n);
+  HGS_HIP(h, hipMemcpyAsync(cells.data(), t->vg.cells, (size_t)n * sizeof(NdtCellRec), hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n; i++) {
+    int key;
+    std::memcpy(&key, &cells[i].v1.w, 4);
+    if (ijk3) {
+      const int m1 = meta.vg_div_mul[1], m2 = meta.vg_div_mul[2];
+      ijk3[3 * i] = key % m1 + meta.vg_min_b[0];
+      ijk3[3 * i + 1] = (key % m2) / m1 + meta.vg_min_b[1];
+      ijk3[3 * i + 2] = key / m2 + meta.vg_min_b[2];
+    }
+    if (mean3) mean3[3 * i] = cells[i].mean[0], mean3[3 * i + 1] = cells[i].mean[1], mean3[3 * i + 2] = cells[i].mean[2];
+    if (cov6) {
+      float* o = cov6 + 6 * i;
       o[0] = cells[i].v0.x, o[1] = cells[i].v0.y, o[2] = cells[i].v0.z, o[3] = cells[i].v0.w, o[4] = cells[i].v1.x, o[5] = cells[i].v1.y;
     }
     if (npts) npts[i] = (int)cells[i].v1.z;

@@ -328,6 +328,17 @@ class RegistrationHIP:
         k = min(n.value, cap)
         return ijk[:k].copy(), mean[:k].copy(), icov[:k].copy(), npts[:k].copy()
 
+    def vgicp_voxels(self, cap: int = 1 << 20):
+        """The FAST_VGICP target's Gaussian voxel map: (integer voxel coordinates [m, 3], means [m, 3] in double, the stored float covariances
+        [m, 6] = xx, xy, xz, yy, yz, zz, points per voxel [m]), in no particular order."""
+        ijk, mean, cov, npts = np.zeros((cap, 3), np.int32), np.zeros((cap, 3)), np.zeros((cap, 6), np.float32), np.zeros(cap, np.int32)
+        n = C.c_int32()
+        vp = C.c_void_p
+        self._check(L.lib().hgs_debug_vgicp_voxels(self._h, cap, ijk.ctypes.data_as(vp), mean.ctypes.data_as(vp), cov.ctypes.data_as(vp),
+                                                   npts.ctypes.data_as(vp), C.byref(n)))
+        k = min(n.value, cap)
+        return ijk[:k].copy(), mean[:k].copy(), cov[:k].copy(), npts[:k].copy()
+
     def ndt_derivatives(self, p6):
         p = np.ascontiguousarray(p6, np.float64)
         s, g, H = np.zeros(1), np.zeros(6), np.zeros((6, 6))

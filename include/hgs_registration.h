@@ -152,7 +152,12 @@ int hgs_set_target_cloud(hgs_handle* h, hgs_cloud* c); /* borrowed, must outlive
 /* setInputSource — scan_matching_odometry_nodelet.cpp:177 ; loop_detector.hpp:136 */
 int hgs_set_source(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes);
 int hgs_set_source_cloud(hgs_handle* h, hgs_cloud* c);
-/* align(output, guess) + hasConverged() + getFinalTransformation() — odometry_nodelet.cpp:210-220 ; loop_detector.hpp:143-153 */
+/* align(output, guess) + hasConverged() + getFinalTransformation() — odometry_nodelet.cpp:210-220 ; loop_detector.hpp:143-153
+ * Deviation from fast_gicp, stated: HGS_FAST_VGICP addresses the target's voxels by a 32-bit linear key over the bounding box of
+ * the target's voxel coordinates floor(p / resolution - 0.5) (fast_gicp's GaussianVoxelMap hashes the three coordinates and has no such limit).  A target
+ * whose box holds more than INT_MAX = 2147483647 cells (1291 cells per axis; one stray return 1.3 km away at resolution 1.0) has no map: hgs_align,
+ * hgs_loop_match_batch[_sharded] and hgs_debug_gicp_linearize / hgs_debug_vgicp_voxels return HGS_ERR_UNSUPPORTED, hgs_last_error() names the grid size,
+ * and the engine stays usable (set another target, or remove the stray points: the prefilter's distance filter does). */
 int hgs_align(hgs_handle* h, const float guess[16], hgs_result* out);
 /* The `output` cloud of align(): out_pts[i].xyz = T * source[i].xyz (records of stride_bytes; other bytes untouched). */
 int hgs_transform_source(hgs_handle* h, const float T[16], void* out_pts, size_t stride_bytes);
@@ -364,6 +369,11 @@ int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_para
 int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint32_t i0, uint32_t n, int32_t* counts, double* coeffs4);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
+/* Voxels of the FAST_VGICP target's Gaussian voxel map (any order), built for the engine's resolution and correspondence_randomness if needed:
+ * the voxel's integer coordinate floor(p / resolution - 0.5) per axis (decoded from its linear key), the mean of its points (double), the mean
+ * of their covariances as stored (float: xx,xy,xz,yy,yz,zz) and the number of points.  *n_cells = voxels in the map; the first min(cap, *n_cells)
+ * are written; any of the four arrays may be NULL.  An additive debug symbol: HGS_ABI_VERSION is unchanged (no struct or status code changed). */
+int hgs_debug_vgicp_voxels(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* cov6, int32_t* npts, int32_t* n_cells);
 /* One NDT derivative pass at p = (tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */
 int hgs_debug_ndt_derivatives(hgs_handle* h, const double p6[6], double* score, double* g6, double* H36);
 /* the pure-host merge step of hgs_loop_match_batch_sharded: `gathered` = world blocks of `per` slots, of rank r's block the first

@@ -12,6 +12,7 @@
 //     PCL-1.8-derived code never runs: `interval_converged = (step_max - step_min) > 0`),
 //   * convergence: iter > max_iterations || (iter > 0 && step < transformation_epsilon).
 #pragma once
+#include <climits>
 #include <cstring>
 #include <limits>
 #include <unordered_map>
@@ -66,6 +67,8 @@ public:
       div_b[d] = max_b[d] - min_b[d] + 1;
     }
     divb_mul[0] = 1, divb_mul[1] = div_b[0], divb_mul[2] = (long)div_b[0] * div_b[1];
+    // more cells than an int indexes: applyFilter gives up and the grid stays without a cell
+    if ((long long)div_b[0] * div_b[1] * div_b[2] > (long long)INT_MAX) return;
     for (const P3f& p : pts) {
       const int ijk[3] = {cell_coord(p.x), cell_coord(p.y), cell_coord(p.z)};
       NdtCell& c = leaves[key_of(ijk)];

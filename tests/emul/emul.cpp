@@ -542,6 +542,23 @@ int emul_ndt_grid(EmulHandle* h, int32_t* min_b, int32_t* div_mul) {
   for (int k = 0; k < 3; k++) min_b[k] = h->ndt.grid.min_b[k], div_mul[k] = h->ndt.grid.div_mul[k];
   return 0;
 }
+// the VGICP voxel map of the target: linear key, mean, stored float covariance, count (the decoding of the key: emul_vgicp_grid)
+int emul_vgicp_voxels(EmulHandle* h, int cap, int32_t* key, double* mean3, float* cov6, int32_t* npts) {
+  const int n = (int)h->vg.cells.size();
+  for (int i = 0; i < n && i < cap; i++) {
+    const NdtCellRec& r = h->vg.cells[i];
+    key[i] = float_as_int_hd(r.v1.w);
+    mean3[3 * i] = r.mean[0], mean3[3 * i + 1] = r.mean[1], mean3[3 * i + 2] = r.mean[2];
+    float* o = cov6 + 6 * i;
+    o[0] = r.v0.x, o[1] = r.v0.y, o[2] = r.v0.z, o[3] = r.v0.w, o[4] = r.v1.x, o[5] = r.v1.y;
+    npts[i] = (int)r.v1.z;
+  }
+  return n;
+}
+int emul_vgicp_grid(EmulHandle* h, int32_t* min_b, int32_t* div_mul) {
+  for (int k = 0; k < 3; k++) min_b[k] = h->vg.grid.min_b[k], div_mul[k] = h->vg.grid.div_mul[k];
+  return 0;
+}
 int emul_ndt_derivatives(EmulHandle* h, const double* p6, double* score, double* g6, double* H36) {
   const NdtConsts c = ndt_consts(h->prm);
   NdtAngles ang;

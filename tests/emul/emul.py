@@ -40,6 +40,8 @@ def lib():
         L.emul_gicp_linearize.argtypes = [vp, vp, vp, vp, vp, vp]
         L.emul_ndt_cells.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.emul_ndt_grid.argtypes = [vp, vp, vp]
+        L.emul_vgicp_voxels.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        L.emul_vgicp_grid.argtypes = [vp, vp, vp]
         L.emul_ndt_derivatives.argtypes = [vp, vp, vp, vp, vp]
         L.emul_sorted_order.argtypes = [vp, C.c_int, vp]
         L.emul_walk_stats.argtypes = [vp, vp, C.c_float, C.c_int, vp]
@@ -119,6 +121,16 @@ class EmulRegistration:
         key = key[:n]
         ijk = np.stack([key % mul[1], (key // mul[1]) % (mul[2] // mul[1]), key // mul[2]], 1) + min_b
         return ijk, mean[:n].copy(), icov[:n].copy(), npts[:n].copy()
+
+    def vgicp_voxels(self):
+        cap = 1 << 20
+        key, mean, cov, npts = np.zeros(cap, np.int32), np.zeros((cap, 3)), np.zeros((cap, 6), np.float32), np.zeros(cap, np.int32)
+        n = lib().emul_vgicp_voxels(self._h, cap, _p(key), _p(mean), _p(cov), _p(npts))
+        min_b, mul = np.zeros(3, np.int32), np.zeros(3, np.int32)
+        lib().emul_vgicp_grid(self._h, _p(min_b), _p(mul))
+        key = key[:n]
+        ijk = np.stack([key % mul[1], (key % mul[2]) // mul[1], key // mul[2]], 1) + min_b
+        return ijk, mean[:n].copy(), cov[:n].copy(), npts[:n].copy()
 
     def ndt_derivatives(self, p6):
         p = np.ascontiguousarray(p6, np.float64)

@@ -244,18 +244,36 @@ def ndt_newton_step(g, H, step_size=0.1, trans_eps=0.01):
     return dp, max(min(n, step_size), trans_eps / 2)
 
 
-def vgicp_linearize(src, tgt, cov_s, cov_t, T, resolution, offsets=((0, 0, 0),)):
-    """fast_gicp::FastVGICP (ADDITIVE voxels, SURVEY Appendix A.3): voxel = {n, mean of the points, mean of their
-    covariances}, key floor(p / res - 0.5); every source point is matched against the voxel(s) of T a_i with weight
-    sqrt(n).  Returns H, b, error and the number of voxel correspondences per source point."""
-    src, tgt = np.asarray(src, np.float64), np.asarray(tgt, np.float64)
-    key_t = np.floor(tgt / resolution - 0.5).astype(np.int64)
-    vox = {}
-    for k, p, c in zip(map(tuple, key_t), tgt, cov_t):
-        v = vox.setdefault(k, [0, np.zeros(3), np.zeros((3, 3))])
+def sym3(c6):
+    """[n, 6] (xx, xy, xz, yy, yz, zz) -> [n, 3, 3] symmetric matrices."""
+    c6 = np.asarray(c6, np.float64)
+    return c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
+
+
+def vgicp_voxels(xyz, cov, resolution):
+    """fast_gicp's GaussianVoxelMap (ADDITIVE) in float64 throughout: dict (i, j, k) -> (n, mean of the points,
+    mean of their covariances [3, 3]) with the key floor(float64(p) / resolution - 0.5); non-finite points belong to no voxel.
+    cov: [n, 3, 3], or [n, 6] = xx, xy, xz, yy, yz, zz."""
+    xyz, cov = np.asarray(xyz, np.float64).reshape(-1, 3), np.asarray(cov, np.float64)
+    if cov.ndim == 2:
+        cov = sym3(cov)
+    finite = np.isfinite(xyz).all(axis=1)
+    keys = np.floor(xyz[finite] / np.float64(resolution) - 0.5).astype(np.int64)
+    sums = {}
+    for k, p, c in zip(map(tuple, keys), xyz[finite], cov[finite]):
+        v = sums.setdefault(k, [0, np.zeros(3), np.zeros((3, 3))])
         v[0] += 1
         v[1] += p
         v[2] += c
+    return {k: (v[0], v[1] / v[0], v[2] / v[0]) for k, v in sums.items()}
+
+
+def vgicp_linearize(src, tgt, cov_s, cov_t, T, resolution, offsets=((0, 0, 0),)):
+    """fast_gicp::FastVGICP (ADDITIVE voxels, SURVEY Appendix A.3): voxel = {n, mean of the points, mean of their
+    covariances}, key floor(p / res - 0.5) (vgicp_voxels); every source point is matched against the voxel(s) of T a_i with weight
+    sqrt(n).  Returns H, b, error and the number of voxel correspondences per source point."""
+    src, tgt = np.asarray(src, np.float64), np.asarray(tgt, np.float64)
+    vox = vgicp_voxels(tgt, cov_t, resolution)
     R, t = T[:3, :3], T[:3, 3]
     q = src @ R.T + t
     key_s = np.floor(q / resolution - 0.5).astype(np.int64)
@@ -266,7 +284,7 @@ def vgicp_linearize(src, tgt, cov_s, cov_t, T, resolution, offsets=((0, 0, 0),))
             if v is None:
                 continue
             hits[i] += 1
-            n, mean, cov = v[0], v[1] / v[0], v[2] / v[0]
+            n, mean, cov = v
             M = np.sqrt(n) * np.linalg.inv(cov + R @ cov_s[i] @ R.T)
             e = mean - q[i]
             J = np.hstack([skew(q[i]), -np.eye(3)])

@@ -373,10 +373,56 @@ def tie_heavy_cloud(seed: int = 0) -> np.ndarray:
     return synth.to_xyzi(out[rng.permutation(len(out))])
 
 
+def span_target(tgt, spans, coord_of):
+    """`tgt` with ONE point moved so that the voxel bounding box spans exactly spans[d] cells on axis d: coord_of(xyz float32 [n, 3]) -> the integer
+    cell coordinates the engine under test uses.  The moved point is one that is extreme on no axis and lands in the middle of its new cell (+0.5 of a
+    cell on every axis in front of its lower face).  Returns (cloud, spans measured on the result with coord_of)."""
+    xyz = synth.xyz_of(tgt)
+    finite = np.isfinite(xyz).all(axis=1)
+    c = coord_of(xyz[finite])
+    lo, hi = c.min(axis=0), c.max(axis=0)
+    inner = np.flatnonzero(finite)[((c > lo) & (c < hi)).all(axis=1)]
+    assert len(inner) > 0
+    want = lo + np.asarray(spans, np.int64) - 1
+    assert (want > hi).all()
+    out = tgt.copy()
+    out["x"][inner[0]], out["y"][inner[0]], out["z"][inner[0]] = cell_middle(coord_of, want)
+    c = coord_of(synth.xyz_of(out)[finite])
+    return out, c.max(axis=0) - c.min(axis=0) + 1
+
+
+def cell_middle(coord_of, cell):
+    """A float32 point in the middle of integer cell `cell` under coord_of (resolution 1.0 grids: NDT's cells start at integers, VGICP's at halves)."""
+    cell = np.asarray(cell, np.int64)
+    for off in (0.5, 1.0):
+        p = (cell + off).astype(np.float32)
+        if np.array_equal(coord_of(p[None])[0], cell) and np.array_equal(coord_of((p + np.float32(0.25))[None])[0], cell) and np.array_equal(
+                coord_of((p - np.float32(0.25))[None])[0], cell):
+            return p
+    raise AssertionError("no cell middle found")
+
+
+def ndt_coord(res):
+    """pclomp::VoxelGridCovariance's cell of a point: floor(p * (1.0f / leaf)) in float (SURVEY Appendix A.1)."""
+    inv = np.float32(1.0) / np.float32(res)
+    return lambda xyz: np.floor(np.asarray(xyz, np.float32) * inv).astype(np.int64)
+
+
+def vgicp_coord(res):
+    """fast_gicp GaussianVoxelMap's voxel of a point: floor(p / resolution - 0.5) in double."""
+    return lambda xyz: np.floor(np.asarray(xyz, np.float64) / np.float64(res) - 0.5).astype(np.int64)
+
+
+INT_MAX = 2 ** 31 - 1
+
+
 def check_ndt_edge_cases(make_engine):
     """NDT inputs the nodelets can produce at the borders: an empty source, a source that meets no target cell at all, a target
     without a single valid cell (fewer than 6 points per voxel everywhere), non-finite points, and a one-point source.  The
-    engine must terminate, agree with the oracle's exact-sum mode on convergence flag, iteration count and pose, and survive."""
+    engine must terminate, agree with the oracle's exact-sum mode on convergence flag, iteration count and pose, and survive.
+    And pcl's limit on the grid: a target whose bounding box spans 1290 cells per axis (1290^3 <= INT_MAX) is voxelised as usual, one that
+    spans 1291 per axis has no cells at all (VoxelGridCovariance::applyFilter gives up, SURVEY Appendix A.1) and registers like the
+    target without valid cells."""
     tgt, src, T = synth.make_pair("VLP-16", 1, downsample=0.4)
     p = O.default_params(O.HGS_NDT_OMP)
     p.resolution = 1.0
@@ -386,20 +432,33 @@ def check_ndt_edge_cases(make_engine):
     with_nan = src.copy()
     with_nan["x"][::7] = np.nan
     with_nan["z"][3::11] = np.inf
+    wide = {}
+    for S in (1290, 1291):
+        wide[S], spans = span_target(tgt, (S, S, S), ndt_coord(p.resolution))
+        assert list(spans) == [S, S, S] and (int(np.prod(spans)) > INT_MAX) == (S == 1291), spans
     cases = [("empty source", tgt, src[:0], np.eye(4)), ("source outside the grid", tgt, far, np.eye(4)), ("target without valid cells", sparse_tgt, src, T),
-             ("non-finite source points", tgt, with_nan, T), ("one-point source", tgt, src[100:101], T), ("non-finite target points", with_nan, src, np.eye(4))]
+             ("non-finite source points", tgt, with_nan, T), ("one-point source", tgt, src[100:101], T), ("non-finite target points", with_nan, src, np.eye(4)),
+             ("grid of 1290^3 cells", wide[1290], src, T), ("grid of 1291^3 cells", wide[1291], src, T)]
     e = make_engine(p)
+    flags = {}
     for name, t, s, guess in cases:
         o = make_oracle(p).set_ndt_sum_mode(1)
         for r in (e, o):
             r.setInputTarget(t)
             r.setInputSource(s)
+        if name == "grid of 1290^3 cells":
+            check_ndt_cells(e, o)
+            assert len(o.ndt_cells()[0]) > 100
+        if name in ("target without valid cells", "grid of 1291^3 cells"):
+            assert len(e.ndt_cells()[0]) == 0 and len(o.ndt_cells()[0]) == 0, (name, len(e.ndt_cells()[0]), len(o.ndt_cells()[0]))
         re, ro = e.align(guess), o.align(guess)
         assert bool(re.converged) == bool(ro.converged) and re.iterations == ro.iterations, (name, re.converged, ro.converged, re.iterations, ro.iterations)
+        flags[name] = (bool(re.converged), re.iterations, re.lm_tries)
         a, b = re.matrix(), ro.matrix()
         assert np.array_equal(np.isnan(a), np.isnan(b)), name
         if not np.isnan(b).any():
             assert bytes(re.final_transformation) == bytes(ro.final_transformation), (name, synth.pose_error(a, b))
+    assert flags["grid of 1291^3 cells"] == flags["target without valid cells"], flags
     e.close()
 
 
@@ -503,3 +562,254 @@ def check_adapter_lazy_tree_lines(out):
     f = out[9].split()   # the aligned cloud computed on the host (pcl::transformPointCloud's unfused float arithmetic) vs the device's fma chain: float rounding apart
     assert f[0] == "aligned_cloud" and int(f[3]) > 0 and float(f[5]) < 2e-5, out[9]
     assert out[10] == "new_target converged 1 builds 1 output_is_input_copy 1", out[10]
+
+
+# ---- FAST_VGICP: the voxel map looked at directly, and the edge inputs ------------------------------------------------------------------------
+def kernel_block_size():
+    """kBlock of the kernels (threads per block; k_vgicp_build_cells' one-thread-per-sorted-point launch is cut into blocks of it)."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "hdl_graph_slam_amd", "csrc", "hgs_device.h")).read()
+    return int(re.search(r"constexpr int kBlock = (\d+);", text).group(1))
+
+
+def boundary_lattice(res, half=3):
+    """Three mutually orthogonal plane patches (a floor and two walls: a registration against them is well posed) of points at multiples of res / 2 on both
+    sides of zero, every point ON a voxel boundary of floor(p / res - 0.5): the coordinate along its plane's normal is an odd multiple of res / 2 (there
+    p / res - 0.5 is an integer, the lower face of a voxel), and so is every other in-plane coordinate.  res a power of two: exact in float."""
+    a = np.arange(-2 * half, 2 * half + 1)
+    u, v = (m.reshape(-1) for m in np.meshgrid(a, a, indexing="ij"))
+    f = np.full_like(u, -2 * half + 1)
+    g = np.unique(np.concatenate([np.stack([u, v, f], 1), np.stack([f, u, v], 1), np.stack([u, -f, v], 1)]), axis=0)
+    return synth.to_xyzi((g * (res / 2)).astype(np.float32))
+
+
+def vgicp_voxel_cases():
+    """name -> (resolution, cloud, check(voxels, xyz, res)): small targets for check_vgicp_voxels.  `check` asserts, on the numpy reference's voxels alone,
+    that the input exercises what it is there for."""
+    B = kernel_block_size()
+    rng = np.random.default_rng(23)
+    cases = {}
+    scan = synth.make_pair("VLP-16", 1, downsample=0.4)[0]
+
+    def scan_check(vox, xyz, res):
+        n = np.array([v[0] for v in vox.values()])
+        assert len(xyz) > 4 * B and (n == 1).any() and (n >= 4).any() and len(vox) > 2 * B   # several blocks of points and of run heads; short and long runs
+        k = np.array(list(vox))
+        assert (k.min(axis=0) < 0).all() and (k.max(axis=0)[:2] > 0).all()                    # voxels on both sides of zero
+    for res in (1.0, 0.5, 0.3):
+        cases[f"scan at {res}"] = (res, scan, scan_check)
+
+    def float_key_check(vox, xyz, res):
+        # some point's voxel differs when the coordinate is computed in float: what vgicp_coord's double arithmetic is there for
+        k32 = np.floor(xyz.astype(np.float32) / np.float32(res) - np.float32(0.5)).astype(np.int64)
+        assert (k32 != vgicp_coord(res)(xyz)).any()
+    faces = ((rng.integers(-40, 40, (600, 3)) + 0.5) * 0.3).astype(np.float32)
+    near_faces = np.nextafter(faces, np.where(rng.random(faces.shape) < 0.5, -np.inf, np.inf).astype(np.float32))   # one float ulp off a voxel face
+    cases["points next to faces at 0.3"] = (0.3, synth.to_xyzi(near_faces), float_key_check)
+
+    def lattice_check(vox, xyz, res):
+        f = xyz.astype(np.float64) / res - 0.5
+        assert (f == np.floor(f)).any(axis=1).all()                                            # every point lies on a voxel face
+        n = [v[0] for v in vox.values()]
+        assert (xyz < 0).any(axis=0).all() and (xyz > 0).any(axis=0).all() and max(n) >= 4 and min(n) == 1
+    for res in (1.0, 0.5):
+        cases[f"boundary lattice at {res}"] = (res, boundary_lattice(res), lattice_check)
+
+    for count in (3 * B - 1, 3 * B, 3 * B + 1):
+        # one voxel with `count` points (more than two blocks of the sorted array) and a voxel with a higher key behind it, whose run head is thread
+        # B - 1 of a block, thread 0 of the next, and thread 1
+        big = rng.uniform(0.55, 1.45, (count, 3)) + [3.0, -2.0, 1.0]
+        tail = rng.uniform(0.55, 1.45, (7, 3)) + [4.0, -2.0, 1.0]
+        pts = np.concatenate([big, tail])
+
+        def run_check(vox, xyz, res, count=count):
+            assert sorted(v[0] for v in vox.values()) == [7, count] and count > 2 * B
+        cases[f"one voxel of {count} points"] = (1.0, synth.to_xyzi(pts[rng.permutation(len(pts))].astype(np.float32)), run_check)
+
+    cells = rng.permutation(np.stack(np.meshgrid(*[np.arange(-6, 6)] * 3, indexing="ij"), -1).reshape(-1, 3))[: 2 * B + 77]
+    own = (cells + 1.0 + rng.uniform(-0.4, 0.4, cells.shape)) * 0.5
+
+    def own_check(vox, xyz, res):
+        assert len(vox) == len(xyz) > 2 * B
+    cases["every point in its own voxel"] = (0.5, synth.to_xyzi(own.astype(np.float32)), own_check)
+
+    base = rng.uniform(-6, 6, (B - 29, 3)) * [1, 1, 0.3]
+    four = np.repeat(base, 4, axis=0)
+
+    def four_check(vox, xyz, res):
+        assert all(v[0] % 4 == 0 for v in vox.values()) and len(xyz) > 3 * B
+    cases["every point four times"] = (1.0, synth.to_xyzi(four[rng.permutation(len(four))].astype(np.float32)), four_check)
+
+    holes = scan[::4].copy()
+    holes["x"][::7] = np.nan
+    holes["z"][3::11] = np.inf
+    holes["y"][5::13] = -np.inf
+
+    def holes_check(vox, xyz, res):
+        finite = int(np.isfinite(xyz).all(axis=1).sum())
+        assert sum(v[0] for v in vox.values()) == finite < len(xyz) - 100 and finite > 2 * B
+    cases["non-finite points mixed in"] = (1.0, holes, holes_check)
+
+    box = np.stack(np.meshgrid(np.arange(-4, 4), np.arange(-4, 4), np.arange(-5, 6), indexing="ij"), -1).reshape(-1, 3)
+    dense = np.concatenate([box + 1.0 + rng.uniform(-0.3, 0.3, box.shape), box[::3] + 1.0 + rng.uniform(-0.3, 0.3, box[::3].shape)])
+
+    def dense_check(vox, xyz, res):
+        k = np.array(list(vox))
+        span = k.max(axis=0) - k.min(axis=0) + 1
+        assert len(vox) == int(np.prod(span)) > 2 * B                                          # the box is full: the linear keys are 0 .. n - 1 without a gap
+    cases["dense lattice, consecutive keys"] = (1.0, synth.to_xyzi(dense[rng.permutation(len(dense))].astype(np.float32)), dense_check)
+    return cases
+
+
+def check_vgicp_voxels(engine, cloud, res, input_check=None):
+    """The FAST_VGICP target's voxel map (k_vgicp_grid_params / k_vgicp_cell_keys / sort / k_vgicp_build_cells, read back by hgs_debug_vgicp_voxels)
+    against np_reference.vgicp_voxels in float64 on the SAME per-point covariances (the engine's own, hgs_debug_target_covariances: the voxel kernels are
+    judged alone): equal coordinate sets without duplicates, n exactly, the mean within 1e-9 (check_ndt_cells' bound; sums of at most a few hundred
+    coordinates below 100 m re-associated in double: 1e-11), every covariance entry within 2 * 2^-24 of the voxel's largest entry (one float store, times two)."""
+    import np_reference as NP
+    assert engine.params.resolution == res
+    engine.setInputTarget(cloud)
+    xyz = synth.xyz_of(cloud)
+    ref = NP.vgicp_voxels(xyz, engine.target_covariances(len(cloud)).astype(np.float64), res)
+    if input_check is not None:
+        input_check(ref, xyz, res)
+    ijk, mean, cov, n = engine.vgicp_voxels()
+    got = [tuple(int(v) for v in k) for k in ijk]
+    assert len(set(got)) == len(got), f"{len(got) - len(set(got))} voxels appear twice"
+    assert set(got) == set(ref), f"{len(set(got) - set(ref))} voxels the reference does not have, {len(set(ref) - set(got))} missing"
+    rn = np.array([ref[k][0] for k in got])
+    assert np.array_equal(n, rn), f"{(n != rn).sum()} voxels with another point count, e.g. {n[n != rn][:4]} for {rn[n != rn][:4]}"
+    rmean = np.array([ref[k][1] for k in got])
+    assert np.abs(mean - rmean).max() < 1e-9, f"voxel means differ by {np.abs(mean - rmean).max():.3e}"
+    rcov = np.array([ref[k][2] for k in got])[:, [0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]]
+    err = np.abs(cov.astype(np.float64) - rcov).max(axis=1) / np.abs(rcov).max(axis=1)
+    assert err.max() <= 2 * 2.0 ** -24, f"voxel covariances differ by {err.max():.3e} of the voxel's largest entry"
+    return ref
+
+
+def _expect_unsupported(call, *needles):
+    from hdl_graph_slam_amd.registration import HgsError
+    try:
+        call()
+    except HgsError as exc:
+        assert "unsupported" in str(exc) and all(n in str(exc) for n in needles), str(exc)
+        return
+    raise AssertionError("the call succeeded on a target whose voxel map could not be built")
+
+
+def check_vgicp_edge_cases(make_engine):
+    """FAST_VGICP at the border inputs ICP_HIP, NDT_OMP and the prefilter got in their own checks.  Every case: one linearisation (check_gicp_linearize: voxel
+    hits per point exact, H / b / error) and a whole registration within 1e-5 m / 1e-5 rad of the oracle (test_vgicp_align's tolerance) with the same
+    converged flag, iteration and LM-try counts; a loop batch over odd candidates and a target swap, bit for bit against single aligns; and the
+    size limit of the voxel grid: 1290 cells per axis work like any target, 1291 per axis (more than INT_MAX cells) are refused by name."""
+    tgt, src, T = synth.make_pair("VLP-16", 1, downsample=0.4)
+    tol = dict(tol_m=1e-5, tol_rad=1e-5)
+    far = src.copy()
+    far["x"] += 500.0
+    with_nan = src.copy()
+    with_nan["x"][::7] = np.nan
+    with_nan["z"][3::11] = np.inf
+
+    def params(res=1.0, search=O.HGS_DIRECT7):
+        p = O.default_params(O.HGS_FAST_VGICP)
+        p.resolution, p.neighbor_search = res, search
+        return p
+
+    def run(e, p, t, s, guess, name):
+        """t, s: a host cloud, or (resident cloud of `e`, the host cloud it was uploaded from)"""
+        o = make_oracle(p)
+        (et, ot), (es, os_) = (t if isinstance(t, tuple) else (t, t)), (s if isinstance(s, tuple) else (s, s))
+        e.setInputTarget(et), e.setInputSource(es), o.setInputTarget(ot), o.setInputSource(os_)
+        try:
+            check_gicp_linearize(e, o, np.asarray(guess, np.float32).astype(np.float64))
+            return check_align(e, o, guess, **tol)
+        except AssertionError as exc:
+            raise AssertionError(f"{name}: {exc}") from exc
+
+    p = params()
+    e = make_engine(p)
+    ct, cs = e.upload(tgt), e.upload(src)    # (resident: their covariances are computed once for all the cases below)
+    rt, rs = (ct, tgt), (cs, src)
+    for name, t, s, guess in (("empty source", rt, src[:0], np.eye(4)), ("source outside the grid", rt, far, np.eye(4)), ("one-point source", rt, src[100:101], T),
+                              ("non-finite source points", rt, with_nan, T), ("non-finite target points", with_nan, rs, np.eye(4)),
+                              ("target of 7 points", tgt[40:47], rs, T), ("target of 1 point", tgt[40:41], rs, T)):
+        run(e, p, t, s, guess, name)
+
+    # ---- the size limit of the grid
+    wide = {}
+    for S in (1290, 1291):
+        wide[S], spans = span_target(tgt, (S, S, S), vgicp_coord(p.resolution))
+        assert list(spans) == [S, S, S] and (int(np.prod(spans)) > INT_MAX) == (S == 1291), spans
+    o = make_oracle(p)
+    e.setInputTarget(wide[1290]), e.setInputSource(cs), o.setInputTarget(wide[1290]), o.setInputSource(src)
+    check_gicp_linearize(e, o, T.astype(np.float32).astype(np.float64))
+    assert o.gicp_linearize(T)[3].sum() > 1000       # (voxel hits: the map is there)
+    check_align(e, o, T, **tol)
+    e.setInputTarget(wide[1291])
+    size = "1291 x 1291 x 1291"
+    _expect_unsupported(lambda: e.align(T), size)
+    _expect_unsupported(lambda: e.align(T), size)                       # (the cached verdict of the map build)
+    _expect_unsupported(lambda: e.gicp_linearize(T), size)
+    _expect_unsupported(lambda: e.loop_match_batch([cs], [T.astype(np.float32)], 4.0), size)
+    _expect_unsupported(lambda: e.vgicp_voxels(), size)
+    fresh = make_engine(p)
+    fresh.setInputTarget(tgt), fresh.setInputSource(src)
+    want = fresh.align(T)
+    e.setInputTarget(ct)                                                # the engine stays usable: an ordinary target, the result of a fresh engine
+    got = e.align(T)
+    assert (bytes(got.final_transformation), got.converged, got.iterations, got.lm_tries, got.error) == (
+        bytes(want.final_transformation), want.converged, want.iterations, want.lm_tries, want.error)
+
+    # ---- a loop batch over odd candidates equals the sequential aligns, bit for bit
+    cands = [src, far, src[100:101], with_nan, src[::3], src[1000:1300]]
+    guesses = [T, np.eye(4), T, T, T, T]
+    clouds = [e.upload(c) for c in cands]
+    rec, best = e.loop_match_batch(clouds, [np.asarray(g, np.float32) for g in guesses], 4.0)
+    from hdl_graph_slam_amd.registration import select_best
+    assert best == select_best(rec)
+    for i, c in enumerate(clouds):
+        e.setInputSource(c)
+        r = e.align(guesses[i])
+        assert bytes(r.final_transformation) == rec["final_transformation"][i].tobytes(), i
+        assert (r.converged, r.iterations, r.lm_tries, r.error) == (rec["converged"][i], rec["iterations"][i], rec["lm_tries"][i], rec["error"][i]), i
+        assert e.getFitnessScore(4.0) == rec["fitness_score"][i], i
+    assert rec["converged"][0] == 1 and rec["num_inliers"][0] > 1000
+
+    # ---- a target swap inside one engine, to another cloud and back (the cached map of the first target is used again)
+    tgt2 = synth.make_pair("VLP-16", 2, downsample=0.4)[0][::2]
+    ct2 = e.upload(tgt2)
+    seq = []
+    for t in (ct, ct2, ct):
+        e.setInputTarget(t), e.setInputSource(cs)
+        r = e.align(T)
+        seq.append((bytes(r.final_transformation), r.converged, r.iterations, r.lm_tries, r.error))
+    fresh.setInputTarget(tgt2)
+    w2 = fresh.align(T)
+    w1 = (bytes(want.final_transformation), want.converged, want.iterations, want.lm_tries, want.error)
+    assert seq == [w1, (bytes(w2.final_transformation), w2.converged, w2.iterations, w2.lm_tries, w2.error), w1]
+    fresh.close()
+    e.close()
+
+    # ---- other parameters
+    p27 = params(search=O.HGS_DIRECT27)
+    e = make_engine(p27)
+    run(e, p27, tgt[::60], src, T, "sparse target, DIRECT27")
+    e.close()
+    lat = boundary_lattice(1.0)
+    quarter = synth.pose_matrix([0.25, 0.25, 0.25], [0.0, 0.0, 0.0])
+    for search in (O.HGS_DIRECT1, O.HGS_DIRECT27):
+        ps = params(search=search)
+        e = make_engine(ps)
+        run(e, ps, lat, lat, quarter, f"boundary lattice against itself, search {search}")
+        e.close()
+    p1000 = params(res=1000.0)
+    e = make_engine(p1000)
+    re, ro = run(e, p1000, tgt, src, T, "resolution 1000")
+    assert not ro.converged and ro.iterations == p1000.max_iterations == 64      # one voxel holds everything: the run does not settle
+    e.close()
+    p005 = params(res=0.05)
+    e = make_engine(p005)
+    run(e, p005, tgt, src, T, "resolution 0.05")
+    e.close()

@@ -124,6 +124,15 @@ def test_vgicp_align(vgicp_case, guess_kind):
     PC.check_align(e, o, guess, tol_m=1e-5, tol_rad=2e-5)
 
 
+@pytest.mark.parametrize("name", sorted(PC.vgicp_voxel_cases()))
+def test_vgicp_voxel_map(name):
+    """vgicp_coord / vgicp_finalize_voxel and the harness' serial map build, voxel by voxel against the float64 numpy reference."""
+    res, cloud, input_check = PC.vgicp_voxel_cases()[name]
+    p = O.default_params(O.HGS_FAST_VGICP)
+    p.resolution = res
+    PC.check_vgicp_voxels(emul.EmulRegistration(p), cloud, res, input_check)
+
+
 @pytest.fixture(scope="module", params=[("hdl32", 1.0, O.HGS_DIRECT7), ("hdl32", 0.5, O.HGS_DIRECT1), ("vlp16", 1.0, O.HGS_DIRECT7),
                                         ("hdl32", 1.0, O.HGS_KDTREE)])
 def ndt_case(request):

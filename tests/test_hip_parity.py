@@ -195,6 +195,24 @@ def test_vgicp_align(vgicp_case, guess_kind):
     assert bytes(a.final_transformation) == bytes(re.final_transformation)   # run-to-run determinism
 
 
+@pytest.mark.parametrize("name", sorted(PC.vgicp_voxel_cases()))
+def test_vgicp_voxel_map(name):
+    """The target's Gaussian voxel map itself — coordinates, point counts, means, covariances of every voxel — against the float64 numpy reference
+    (parity_checks.check_vgicp_voxels), on small targets built to hit the map build's edges (parity_checks.vgicp_voxel_cases)."""
+    res, cloud, input_check = PC.vgicp_voxel_cases()[name]
+    p = O.default_params(O.HGS_FAST_VGICP)
+    p.resolution = res
+    e = _hip(p)
+    PC.check_vgicp_voxels(e, cloud, res, input_check)
+    e.close()
+
+
+def test_vgicp_edge_cases():
+    """Empty / far / one-point / non-finite / tiny / sparse / boundary inputs, extreme resolutions, a mixed loop batch, a target swap and the size
+    limit of the voxel grid (parity_checks.check_vgicp_edge_cases)."""
+    PC.check_vgicp_edge_cases(_hip)
+
+
 @pytest.fixture(scope="module", params=[("hdl32", 1.0, O.HGS_DIRECT7), ("hdl32", 0.5, O.HGS_DIRECT1), ("vlp16", 1.0, O.HGS_DIRECT7), ("hdl32_raw", 1.0, O.HGS_DIRECT7),
                                         ("hdl32", 1.0, O.HGS_KDTREE)])
 def ndt_case(request):

@@ -610,6 +610,21 @@ def test_ndt_edge_cases():
     PC.check_ndt_edge_cases(_engine)
 
 
+@pytest.mark.parametrize("name", sorted(PC.vgicp_voxel_cases()))
+def test_vgicp_voxel_map(name):
+    """k_vgicp_grid_params / k_vgicp_cell_keys / the sort / k_vgicp_build_cells, voxel by voxel against the float64 numpy reference."""
+    res, cloud, input_check = PC.vgicp_voxel_cases()[name]
+    p = O.default_params(O.HGS_FAST_VGICP)
+    p.resolution = res
+    e = _engine(p)
+    PC.check_vgicp_voxels(e, cloud, res, input_check)
+    e.close()
+
+
+def test_vgicp_edge_cases():
+    PC.check_vgicp_edge_cases(_engine)
+
+
 @pytest.mark.parametrize("name", sorted(PFC.outlier_cases()))
 def test_prefilter_outlier_removal_edge_inputs(name):
     """The prefilter's outlier kernels at the bounds of mean_k, small clouds, coincident and non-finite points (prefilter_checks.outlier_cases)."""
