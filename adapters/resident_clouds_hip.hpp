@@ -112,15 +112,20 @@ public:
     return ok;
   }
 
-  // f2 — apps/prefiltering_nodelet.cpp:131-133 (+ the deskewing step of :112,182-243 when `imu_angular_velocity` is given): the filtered cloud comes back
-  // as PointXYZI records (x, y, z, 1, intensity).  The input is a sensor sweep, not a keyframe: it is not cached.
+  // f2 — apps/prefiltering_nodelet.cpp:131-133 (+ the deskewing step of :112,182-243 when `imu_angular_velocity` is given, + the transform into
+  // base_link_frame of :114-129 when `sensor_to_base` is given: Eigen::Matrix4f::data() of the matrix pcl_ros::transformPointCloud would apply): the filtered
+  // cloud comes back as PointXYZI records (x, y, z, 1, intensity).  The input is a sensor sweep, not a keyframe: it is not cached.
   bool prefilter(const Cloud& src, const hgs_prefilter_params& params, const double* imu_angular_velocity, double scan_period, Cloud& out) {
+    return prefilter(src, params, imu_angular_velocity, scan_period, nullptr, out);
+  }
+  bool prefilter(const Cloud& src, const hgs_prefilter_params& params, const double* imu_angular_velocity, double scan_period, const float* sensor_to_base, Cloud& out) {
     std::lock_guard<std::mutex> lock(mutex_);
     if (!enabled_ || src.points.empty()) return false;
     if (!engine()) return false;
     hgs_cloud* filtered = nullptr;
-    bool ok = check(imu_angular_velocity ? hgs_prefilter_deskewed(handle_, src.points.data(), src.points.size(), sizeof(PointT), &params, imu_angular_velocity, scan_period, &filtered)
-                                         : hgs_prefilter(handle_, src.points.data(), src.points.size(), sizeof(PointT), &params, &filtered),
+    bool ok = check(sensor_to_base ? hgs_prefilter_framed(handle_, src.points.data(), src.points.size(), sizeof(PointT), &params, imu_angular_velocity, scan_period, sensor_to_base, &filtered)
+                    : imu_angular_velocity ? hgs_prefilter_deskewed(handle_, src.points.data(), src.points.size(), sizeof(PointT), &params, imu_angular_velocity, scan_period, &filtered)
+                                           : hgs_prefilter(handle_, src.points.data(), src.points.size(), sizeof(PointT), &params, &filtered),
                     "hgs_prefilter");
     if (ok) {
       out.points.resize(hgs_cloud_size(filtered));

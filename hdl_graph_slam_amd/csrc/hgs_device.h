@@ -212,8 +212,11 @@ void launch_map_centers(hipStream_t s, const unsigned long long* keys, const uns
                         int* count_out);
 
 // prefilter (apps/prefiltering_nodelet.cpp)
-void launch_pf_load(hipStream_t s, const float4* staged, int n, float4* out, const float* deskew_w /* null: no deskewing */, double scan_period, int* count_out,
-                    unsigned* meta_out /* [16]: the voxel-grid record, initialised here */);
+struct PfFrame {
+  float rows[12];  // the upper three rows of the sensor -> base_link matrix, row-major (pf_transform_point, hgs_math.h)
+};
+void launch_pf_load(hipStream_t s, const float4* staged, int n, float4* out, const float* deskew_w /* null: no deskewing */, double scan_period,
+                    const PfFrame* frame /* null: no transform */, int* count_out, unsigned* meta_out /* [16]: the voxel-grid record, initialised here */);
 void launch_pf_distance_flags(hipStream_t s, const float4* pts, int n, int use_filter, double near_thresh, double far_thresh, unsigned* keep);
 void launch_pf_compact(hipStream_t s, const float4* in, int n, const unsigned* keep, const unsigned* slot, float4* out, int* count);
 void launch_pf_bbox(hipStream_t s, const float4* pts, const int* count, int cap, unsigned* meta, int dist_filter = 0, double near_thresh = 0, double far_thresh = 0);

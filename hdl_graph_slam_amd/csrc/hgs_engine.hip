@@ -2127,8 +2127,10 @@ extern "C" int hgs_prefilter_params_default(hgs_prefilter_params* p) try {
   return status_of_current_exception(nullptr);
 }
 
-static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const float* deskew_w, double scan_period,
-                          hgs_cloud** out) {
+// the one sequence behind hgs_prefilter, hgs_prefilter_deskewed and hgs_prefilter_framed.  imu_angular_velocity null: no deskewing; sensor_to_base null:
+// no transform (then the launches and their arguments are those of the two older entry points)
+static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
+                          double scan_period, const float* sensor_to_base, hgs_cloud** out) {
   ApiLock lock(h);
   if (!h || !p || !out || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes % 4) != 0 || n > (size_t)1 << 30) return HGS_ERR_INVALID_ARGUMENT;
   if (p->downsample_method < HGS_DOWNSAMPLE_NONE || p->downsample_method > HGS_DOWNSAMPLE_APPROX_VOXELGRID || p->outlier_removal_method < HGS_OUTLIER_NONE ||
@@ -2136,6 +2138,29 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
       (p->outlier_removal_method == HGS_OUTLIER_STATISTICAL && (p->statistical_mean_k < 1 || p->statistical_mean_k > 62)) ||
       (p->outlier_removal_method == HGS_OUTLIER_RADIUS && (!(p->radius_radius > 0) || p->radius_min_neighbors < 0)))
     return HGS_ERR_INVALID_ARGUMENT;
+  // ang_v(x, y, z) as floats, times -1 (:219-220); an empty imu_queue passes the cloud as it is (:184-186)
+  float w[3] = {0.f, 0.f, 0.f};
+  const float* deskew_w = nullptr;
+  if (imu_angular_velocity) {
+    if (!std::isfinite(scan_period)) return HGS_ERR_INVALID_ARGUMENT;
+    for (int a = 0; a < 3; a++) w[a] = -(float)imu_angular_velocity[a];
+    deskew_w = w;
+  } else {
+    scan_period = 0.0;
+  }
+  PfFrame frame_rows;
+  const PfFrame* frame = nullptr;
+  if (sensor_to_base) {  // column-major 4x4: a rigid transform's bottom row; the rotation block is not looked at (pcl::transformPointCloud does not either)
+    bool finite = true;
+    for (int k = 0; k < 16; k++) finite = finite && std::isfinite(sensor_to_base[k]);
+    if (!finite || sensor_to_base[3] != 0.f || sensor_to_base[7] != 0.f || sensor_to_base[11] != 0.f || sensor_to_base[15] != 1.f) {
+      h->err = finite ? "prefilter: the bottom row of sensor_to_base is not 0 0 0 1" : "prefilter: sensor_to_base has a non-finite entry";
+      return HGS_ERR_INVALID_ARGUMENT;
+    }
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) frame_rows.rows[4 * r + c] = sensor_to_base[4 * c + r];
+    frame = &frame_rows;
+  }
   HGS_TRY(set_device(h));
   *out = nullptr;
   StageTimer tm(h, HGS_STAGE_PREFILTER);
@@ -2155,7 +2180,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
   {
     const float4* staged = nullptr;
     if (n > 0) HGS_TRY(upload_points_packed(h, pts, n, stride_bytes, &staged));
-    launch_pf_load(h->stream, staged, (int)n, cur, deskew_w, scan_period, d_count, d_meta);  // (also: d_count = n, d_meta = the empty voxel-grid record)
+    launch_pf_load(h->stream, staged, (int)n, cur, deskew_w, scan_period, frame, d_count, d_meta);  // (also: d_count = n, d_meta = the empty voxel-grid record)
   }
   // VoxelGrid behind the distance filter (every launch file's prefilter): the filter is applied inside the voxel grid's bounding-box and key kernels
   // instead of by flags + scan + compaction in front of them (four launches less; prefilter_fast = 0 keeps the separate pass — A/B, tests)
@@ -2269,18 +2294,21 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
 }
 
 extern "C" int hgs_prefilter(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, hgs_cloud** out) try {
-  return prefilter_impl(h, pts, n, stride_bytes, p, nullptr, 0.0, out);
+  return prefilter_impl(h, pts, n, stride_bytes, p, nullptr, 0.0, nullptr, out);
 } catch (...) {
   return status_of_current_exception(h);
 }
 
 extern "C" int hgs_prefilter_deskewed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
                                       double scan_period, hgs_cloud** out) try {
-  if (!imu_angular_velocity) return prefilter_impl(h, pts, n, stride_bytes, p, nullptr, 0.0, out);  // empty imu_queue: the cloud passes as it is (:184-186)
-  if (!std::isfinite(scan_period)) return HGS_ERR_INVALID_ARGUMENT;
-  // ang_v(x, y, z) as floats, times -1 (:219-220)
-  const float w[3] = {-(float)imu_angular_velocity[0], -(float)imu_angular_velocity[1], -(float)imu_angular_velocity[2]};
-  return prefilter_impl(h, pts, n, stride_bytes, p, w, scan_period, out);
+  return prefilter_impl(h, pts, n, stride_bytes, p, imu_angular_velocity, scan_period, nullptr, out);
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
+                                    double scan_period, const float* sensor_to_base, hgs_cloud** out) try {
+  return prefilter_impl(h, pts, n, stride_bytes, p, imu_angular_velocity, scan_period, sensor_to_base, out);
 } catch (...) {
   return status_of_current_exception(h);
 }

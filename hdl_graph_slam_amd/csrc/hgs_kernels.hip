@@ -2274,10 +2274,13 @@ void launch_vgicp_error(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt
 // of the NDT / VGICP targets with FLOAT centroids accumulated in input order (CentroidPoint semantics).
 // deskew != 0: the deskewing step of cloud_callback (:112, :182-243) on the way in — point i of the sweep rotated back by the
 // first-order rotation of delta_t = scan_period * i / n at the gyro rate w (pf_deskew_point, hgs_math.h).
+// FRAME: the rigid transform into base_link_frame behind it (:114-129), pcl::transformPointCloud's float arithmetic on the floats the deskewing produced
+// (pf_transform_point, hgs_math.h); the matrix travels in the kernel arguments.  Decided at launch: without a transform the kernel is the one it was.
 // (round 6) thread 0 also sets the pipeline's point count and the initial voxel-grid record {bbox min = max uint, bbox max = 0, ...} — two copy
 // kernels less per sweep
+template <bool FRAME>
 __global__ __launch_bounds__(kBlock) void k_pf_load(const float4* __restrict__ staged, int n, float4* __restrict__ out, int deskew, float wx, float wy, float wz, double scan_period,
-                                                    int* __restrict__ count_out, unsigned* __restrict__ meta_out) {
+                                                    int* __restrict__ count_out, unsigned* __restrict__ meta_out, PfFrame frame) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i == 0) {
     *count_out = n;
@@ -2288,11 +2291,16 @@ __global__ __launch_bounds__(kBlock) void k_pf_load(const float4* __restrict__ s
   const float4 p = staged[i];  // {x, y, z, intensity}, packed by the host (upload_points_packed)
   float x = p.x, y = p.y, z = p.z;
   if (deskew) pf_deskew_point(wx, wy, wz, scan_period, i, n, &x, &y, &z);
+  if (FRAME) pf_transform_point(frame.rows, &x, &y, &z);
   out[i] = make_float4(x, y, z, p.w);
 }
-void launch_pf_load(hipStream_t s, const float4* staged, int n, float4* out, const float* deskew_w, double scan_period, int* count_out, unsigned* meta_out) {
-  hipLaunchKernelGGL(k_pf_load, dim3(std::max(1, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, staged, n, out, deskew_w ? 1 : 0, deskew_w ? deskew_w[0] : 0.f,
-                     deskew_w ? deskew_w[1] : 0.f, deskew_w ? deskew_w[2] : 0.f, scan_period, count_out, meta_out);
+void launch_pf_load(hipStream_t s, const float4* staged, int n, float4* out, const float* deskew_w, double scan_period, const PfFrame* frame, int* count_out,
+                    unsigned* meta_out) {
+  const dim3 grid(std::max(1, (n + kBlock - 1) / kBlock));
+  const int deskew = deskew_w ? 1 : 0;
+  const float wx = deskew_w ? deskew_w[0] : 0.f, wy = deskew_w ? deskew_w[1] : 0.f, wz = deskew_w ? deskew_w[2] : 0.f;
+  if (frame) hipLaunchKernelGGL(k_pf_load<true>, grid, dim3(kBlock), 0, s, staged, n, out, deskew, wx, wy, wz, scan_period, count_out, meta_out, *frame);
+  else hipLaunchKernelGGL(k_pf_load<false>, grid, dim3(kBlock), 0, s, staged, n, out, deskew, wx, wy, wz, scan_period, count_out, meta_out, PfFrame{});
 }
 
 // keep[i] = near < |p| < far  (float norm against double thresholds, :170-173); use_filter == 0 keeps everything

@@ -433,6 +433,19 @@ HGS_HD void pf_deskew_point(float wx, float wy, float wz, double scan_period, in
   *z = (vz + iw * uz) + (ix * uy - iy * ux);
 }
 
+// ---- rigid transform of one sweep point into base_link_frame (apps/prefiltering_nodelet.cpp:114-129) ------------------------
+// pcl::transformPointCloud with a float matrix as PCL >= 1.10 computes it (pcl/common/impl/transforms.hpp, Transformer<float>::se3): per row r
+// x * m(r,0) + (y * m(r,1) + (z * m(r,2) + m(r,3))), every product and sum rounded to float, unfused.  `rows`: the upper three rows of the matrix,
+// row-major (rows[4 r + c] = m(r, c)).  A point with a non-finite coordinate passes untouched, as PCL passes it through in a non-dense cloud.
+HGS_HD void pf_transform_point(const float* rows, float* x, float* y, float* z) {
+  HGS_FP_STRICT
+  const float vx = *x, vy = *y, vz = *z;
+  if (!(isfinite(vx) && isfinite(vy) && isfinite(vz))) return;
+  *x = vx * rows[0] + (vy * rows[1] + (vz * rows[2] + rows[3]));
+  *y = vx * rows[4] + (vy * rows[5] + (vz * rows[6] + rows[7]));
+  *z = vx * rows[8] + (vy * rows[9] + (vz * rows[10] + rows[11]));
+}
+
 // ---- symmetric 3x3 eigen decomposition (cyclic Jacobi), eigenvalues ascending, eigenvectors in columns of V ----
 HGS_HD void eig_sym3(const double* A_in, double* w, double* V) {
   HGS_FP_STRICT

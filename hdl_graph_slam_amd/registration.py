@@ -176,20 +176,25 @@ class RegistrationHIP:
     def upload(self, cloud) -> DeviceCloud:
         return DeviceCloud(self, cloud)
 
-    def prefilter(self, cloud, params=None, imu_angular_velocity=None, scan_period: float = 0.1) -> DeviceCloud:
-        """PrefilteringNodelet::cloud_callback (apps/prefiltering_nodelet.cpp:106-136) on the device: [deskewing ->] distance
-        filter -> voxel grid -> outlier removal.  Returns a resident cloud usable as setInputSource / setInputTarget argument.
+    def prefilter(self, cloud, params=None, imu_angular_velocity=None, scan_period: float = 0.1, base_link_transform=None) -> DeviceCloud:
+        """PrefilteringNodelet::cloud_callback (apps/prefiltering_nodelet.cpp:106-136) on the device: [deskewing ->] [transform into
+        base_link_frame ->] distance filter -> voxel grid -> outlier removal.  Returns a resident cloud usable as setInputSource / setInputTarget argument.
         imu_angular_velocity: the angular_velocity of the sensor_msgs/Imu sample `select_imu_sample` picks (None = the
-        nodelet's empty imu_queue or deskewing off: no deskewing)."""
+        nodelet's empty imu_queue or deskewing off: no deskewing).  base_link_transform: the 4x4 sensor -> base_link matrix the nodelet hands to
+        pcl_ros::transformPointCloud (:114-129), in numpy's row-major layout (None = no base_link_frame: no transform)."""
         if params is None:
             params = L.HgsPrefilterParams()
             self._check(L.lib().hgs_prefilter_params_default(C.byref(params)))
         arr, n, stride = L.cloud_args(cloud)
         h = C.c_void_p()
-        if imu_angular_velocity is None:
+        w = None if imu_angular_velocity is None else np.ascontiguousarray(imu_angular_velocity, np.float64).reshape(3)
+        if base_link_transform is not None:
+            m = L.colmajor16(base_link_transform)
+            self._check(L.lib().hgs_prefilter_framed(self._h, arr.ctypes.data_as(C.c_void_p), n, stride, C.byref(params),
+                                                     None if w is None else w.ctypes.data_as(C.c_void_p), float(scan_period), L.fptr(m), C.byref(h)))
+        elif w is None:
             self._check(L.lib().hgs_prefilter(self._h, arr.ctypes.data_as(C.c_void_p), n, stride, C.byref(params), C.byref(h)))
         else:
-            w = np.ascontiguousarray(imu_angular_velocity, np.float64).reshape(3)
             self._check(L.lib().hgs_prefilter_deskewed(self._h, arr.ctypes.data_as(C.c_void_p), n, stride, C.byref(params), w.ctypes.data_as(C.c_void_p),
                                                        float(scan_period), C.byref(h)))
         return DeviceCloud._adopt(self, h)

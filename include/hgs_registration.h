@@ -265,6 +265,17 @@ int hgs_prefilter(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes,
  * host logic).  NULL = the nodelet's empty imu_queue: no deskewing.  scan_period: rosparam "scan_period" (0.1). */
 int hgs_prefilter_deskewed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
                            double scan_period, hgs_cloud** out);
+/* The same with the rigid transform into base_link_frame between the deskewing and the distance filter (apps/prefiltering_nodelet.cpp:114-129; every
+ * launch file sets base_link_frame): deskewing -> transform -> distance_filter -> downsample -> outlier_removal, the order of cloud_callback.
+ * sensor_to_base: the float 4x4 matrix handed to pcl::transformPointCloud, column-major (Eigen::Matrix4f::data()); NULL = no base_link_frame: no
+ * transform, and the call is hgs_prefilter_deskewed.  Turning the tf::StampedTransform of the lookup (:121-127) into that float matrix stays host code of
+ * the caller.  Arithmetic: PCL >= 1.10's, per row x*m(r,0) + (y*m(r,1) + (z*m(r,2) + m(r,3))) in unfused floats, applied to the floats the deskewing
+ * produced; a point with a non-finite coordinate passes untouched (PCL's non-dense path), the intensity is carried along.  PCL 1.8 sums in another order
+ * (DESIGN.md).  HGS_ERR_INVALID_ARGUMENT for a matrix with a non-finite entry or a bottom row other than 0 0 0 1; the rotation block is not checked for
+ * orthogonality (PCL does not check it either). */
+int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p,
+                         const double* imu_angular_velocity /* NULL: no deskewing */, double scan_period,
+                         const float sensor_to_base[16] /* column-major, NULL: no transform */, hgs_cloud** out);
 /* Copy a resident cloud back: out_pts[i] = {x, y, z, (1.0), intensity, ...} with the PointXYZI layout for stride >= 20,
  * packed xyz(+w) otherwise.  Needs room for hgs_cloud_size(c) records. */
 int hgs_cloud_download(hgs_cloud* c, void* out_pts, size_t stride_bytes);
