@@ -87,6 +87,48 @@ public:
     return ok;
   }
 
+  // f1 for every edge of one graph update — the odometry edges of flush_keyframe_queue (apps/hdl_graph_slam_nodelet.cpp:235) and the loop edges behind them
+  // (apps/hdl_graph_slam_nodelet.cpp:569) — in ONE hgs_calc_fitness_score_batch: every cloud of the call is resolved (uploaded when new) first, then one
+  // device call.  (*scores)[i] is what fitness_score returns for pairs[i], bit for bit.  false on any failure — and for a pair fitness_score itself would hand
+  // back to the CPU (a null cloud, an empty cloud1): the caller then runs its per-edge path.
+  struct EdgePair {
+    CloudConstPtr cloud1, cloud2;
+    float relpose[16];  // relpose.cast<float>().matrix().data()
+  };
+  bool fitness_scores(const std::vector<EdgePair>& pairs, double max_range, std::vector<double>* scores) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    if (!enabled_ || !scores) return false;
+    for (const EdgePair& p : pairs)
+      if (!p.cloud1 || !p.cloud2 || p.cloud1->points.empty()) return false;
+    scores->assign(pairs.size(), 1.7976931348623157e308);  // (an empty cloud2: nr == 0 -> DBL_MAX, :76-79; nothing to launch for it)
+    std::vector<size_t> which;
+    for (size_t i = 0; i < pairs.size(); i++)
+      if (!pairs[i].cloud2->points.empty()) which.push_back(i);
+    if (which.empty()) return true;
+    if (!engine()) return false;
+    const uint64_t tick = ++tick_;
+    std::vector<hgs_cloud*> c1, c2;
+    std::vector<float> poses;
+    bool ok = true;
+    for (size_t i : which) {
+      hgs_cloud* a = resident_cloud(pairs[i].cloud1, tick);
+      hgs_cloud* b = a ? resident_cloud(pairs[i].cloud2, tick) : nullptr;
+      if (!a || !b) {
+        ok = false;
+        break;
+      }
+      c1.push_back(a), c2.push_back(b);
+      poses.insert(poses.end(), pairs[i].relpose, pairs[i].relpose + 16);
+    }
+    std::vector<double> dev(which.size());
+    ok = ok && check(hgs_calc_fitness_score_batch(handle_, c1.data(), c2.data(), poses.data(), which.size(), max_range, dev.data(), nullptr), "hgs_calc_fitness_score_batch");
+    enforce_capacity(tick);  // (on every exit path behind the first upload)
+    if (!ok) return false;
+    for (size_t k = 0; k < which.size(); k++) (*scores)[which[k]] = dev[k];
+    device_calls_++;
+    return true;
+  }
+
   // f3 — map_cloud_generator.cpp:13-51 for resolution > 0: the voxel centres of pcl::octree in the octree's own order, intensity 0.
   // `poses_colmajor`: keyframe->pose.matrix().cast<float>() of every snapshot, 16 floats each.
   bool map_cloud(const std::vector<CloudConstPtr>& keyframe_clouds, const std::vector<float>& poses_colmajor, double resolution, Cloud& out) {

@@ -104,12 +104,12 @@ EXPORTS = [
     "hgs_cloud_create", "hgs_cloud_destroy", "hgs_cloud_size", "hgs_cloud_device_bytes", "hgs_cloud_invalidate",
     "hgs_set_target", "hgs_set_target_cloud", "hgs_set_source", "hgs_set_source_cloud",
     "hgs_align", "hgs_transform_source", "hgs_fitness", "hgs_nn_target",
-    "hgs_loop_match_batch", "hgs_loop_match_groups", "hgs_select_best", "hgs_calc_fitness_score",
+    "hgs_loop_match_batch", "hgs_loop_match_groups", "hgs_select_best", "hgs_calc_fitness_score", "hgs_calc_fitness_score_batch",
     "hgs_comm_get_unique_id", "hgs_comm_init", "hgs_comm_finalize", "hgs_loop_match_batch_sharded",
     "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_prefilter_framed", "hgs_cloud_download", "hgs_map_cloud_generate",
     "hgs_floor_params_default", "hgs_detect_floor", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
-    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_vgicp_voxels", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
+    "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_vgicp_voxels", "hgs_debug_cloud_seed_grid", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
 ]
 
 _lib = None
@@ -152,6 +152,7 @@ def lib():
     L.hgs_comm_finalize.argtypes = [vp]
     L.hgs_loop_match_batch_sharded.argtypes = [vp, C.POINTER(vp), sz, vp, vp, sz, C.c_double, vp, C.POINTER(C.c_int32)]
     L.hgs_calc_fitness_score.argtypes = [vp, vp, vp, fp, C.c_double, C.POINTER(C.c_double)]
+    L.hgs_calc_fitness_score_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp, sz, C.c_double, vp, vp]
     L.hgs_prefilter_params_default.argtypes = [C.POINTER(HgsPrefilterParams)]
     L.hgs_prefilter.argtypes = [vp, vp, sz, sz, C.POINTER(HgsPrefilterParams), C.POINTER(vp)]
     L.hgs_prefilter_deskewed.argtypes = [vp, vp, sz, sz, C.POINTER(HgsPrefilterParams), vp, C.c_double, C.POINTER(vp)]
@@ -172,6 +173,7 @@ def lib():
     L.hgs_debug_icp_step.argtypes = [vp, vp, vp, C.c_double, C.c_int32, vp, vp, vp]
     L.hgs_debug_ndt_cells.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
     L.hgs_debug_vgicp_voxels.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+    L.hgs_debug_cloud_seed_grid.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_int32), C.POINTER(sz)]
     L.hgs_debug_ndt_derivatives.argtypes = [vp, vp, vp, vp, vp]
     L.hgs_debug_merge_shard_records.argtypes = [vp, vp, C.c_int32, C.c_size_t, C.c_size_t, vp, vp]
     _lib = L

@@ -153,6 +153,16 @@ void launch_nn_query(hipStream_t s, TargetView tgt, const float4* q, int nq, int
 // seed grid of a target cloud: every sorted point enters three direct-mapped tables (cells of 0.25 / 1 / 4 m, sizes 2^bits, 2^(bits-2), 2^(bits-4))
 void launch_seed_grid_build(hipStream_t s, const float4* pts, const CloudMeta* meta, int n_max, unsigned* tab, int bits);
 inline size_t seed_grid_entries(int bits) { return ((size_t)1 << bits) + ((size_t)1 << (bits - 2)) + ((size_t)1 << (bits - 4)); }
+// ... of several clouds in two launches (one clear, one fill; hgs_calc_fitness_score_batch): jobs[j] on the device, one per cloud; every table is word for
+// word what launch_seed_grid_build writes for that cloud behind a 0xff clear
+struct SeedGridJob {
+  const float4* pts;      // the cloud's sorted points (CloudDesc::pts)
+  const CloudMeta* meta;  // nvalid
+  unsigned* tab;          // seed_grid_entries(bits) words
+  int bits;
+  int pad;
+};
+void launch_seed_grid_build_batch(hipStream_t s, const SeedGridJob* jobs, int njobs, size_t max_entries, int max_n);
 void launch_transform(hipStream_t s, const float4* raw, int n, const float* T16_colmajor_dev, float4* out);
 
 void launch_ndt_grid_params(hipStream_t s, CloudDesc desc, float inv_leaf);

@@ -147,6 +147,8 @@ struct hgs_handle {
   DeviceBuffer lane_partials[7], lane_partials_err[7];
   DeviceBuffer ndt_accum;  // NdtAccum per problem of the running NDT batch
   DeviceBuffer group_tviews, group_corr;  // hgs_loop_match_groups: one TargetView and one correspondence scratch per problem (run_group_batch)
+  DeviceBuffer seed_jobs;                 // ensure_seed_grids: one SeedGridJob per cloud of the list
+  int pair_chunk = 0;                     // hgs_calc_fitness_score_batch: pairs per launch (0: what grid.y holds, 65535); the results do not depend on it (tests)
   hgs::Comm* comm = nullptr;            // hgs_comm_init: the ranks of a sharded loop-closure batch
   DeviceBuffer comm_send, comm_recv, comm_ids;
   DeviceBuffer pf_ukeys;         // prefilter: the voxels' keys in output order (k_pf_grid_radius_flags)
@@ -700,6 +702,40 @@ int ensure_seed_grid(hgs_handle* h, hgs_cloud* c) {
   return HGS_OK;
 }
 
+// The same for every cloud of a list that lacks one (hgs_calc_fitness_score_batch: the distinct tree sides of a graph update's edges): ONE clearing and
+// ONE filling launch over a job list instead of a memset and a launch per cloud; every table is word for word what ensure_seed_grid builds.
+int ensure_seed_grids(hgs_handle* h, const std::vector<hgs_cloud*>& all) {
+  if (!h->seed_grid) return HGS_OK;
+  std::vector<hgs_cloud*> todo;
+  for (hgs_cloud* c : all)
+    if (!c->has_seed && c->has_index && c->n_input > 0 && std::find(todo.begin(), todo.end(), c) == todo.end()) todo.push_back(c);
+  constexpr size_t kMaxJobs = 65535;  // grid.y of one launch
+  for (size_t start = 0; start < todo.size(); start += kMaxJobs) {
+    const size_t nj = std::min(kMaxJobs, todo.size() - start);
+    std::vector<SeedGridJob> jobs(nj);
+    size_t max_entries = 0;
+    int max_n = 0;
+    for (size_t j = 0; j < nj; j++) {
+      hgs_cloud* c = todo[start + j];
+      int bits = 12;
+      while (bits < 24 && ((size_t)1 << bits) < 4 * c->n_input) bits++;
+      const size_t entries = seed_grid_entries(bits);
+      if (!c->seed_block.p || c->seed_bits != bits) {
+        HGS_HIP(h, c->seed_block.alloc(entries * sizeof(unsigned)));
+        c->seed_bits = bits;
+      }
+      jobs[j] = SeedGridJob{c->desc.pts, c->desc.meta, c->seed_block.as<unsigned>(), bits, 0};
+      max_entries = std::max(max_entries, entries), max_n = std::max(max_n, (int)c->n_input);
+    }
+    HGS_HIP(h, h->seed_jobs.reserve(nj * sizeof(SeedGridJob)));
+    HGS_HIP(h, h->up.upload(h->seed_jobs.p, jobs.data(), nj * sizeof(SeedGridJob), h->stream));
+    launch_seed_grid_build_batch(h->stream, h->seed_jobs.as<SeedGridJob>(), (int)nj, max_entries, max_n);
+    HGS_HIP(h, hipGetLastError());
+    for (size_t j = 0; j < nj; j++) todo[start + j]->has_seed = true;
+  }
+  return HGS_OK;
+}
+
 // (HGS_TRACE: device-side per-iteration trace, parity debugging; the mapping itself is hgs_consts.h)
 NdtConsts engine_ndt_consts(const hgs_params& p) {
   NdtConsts c = ndt_consts(p);
@@ -1242,6 +1278,45 @@ int fetch_results(hgs_handle* h, int B, std::vector<DevResult>& out) {
 // pcl::Registration::getFitnessScore: the mean squared distance of the inliers, DBL_MAX without any
 double fitness_score(const DevResult& d) { return d.fit_count > 0 ? d.fit_sum / (double)d.fit_count : std::numeric_limits<double>::max(); }
 
+// hgs_calc_fitness_score_batch: pair i scores cloud2[i], moved by relposes[i], against the tree of cloud1[i] — every edge of a graph update
+// (hdl_graph_slam_nodelet.cpp:235,569) in one chain: one index build and one seed-grid build over the clouds that lack them, then per chunk of pairs
+// one upload each of the target views, the descriptors and the poses, k_fitness<const TargetView*> + k_fitness_final, one copy back and one
+// synchronisation.  No pair reads corr[] (use_seed = 0), so a cloud may repeat in any role; neither h->target nor h->source is read or written.
+int run_pair_fitness(hgs_handle* h, hgs_cloud* const* cloud1, hgs_cloud* const* cloud2, const float* relposes, size_t n_pairs, double max_range,
+                     std::vector<DevResult>& out) {
+  std::vector<hgs_cloud*> all(cloud2, cloud2 + n_pairs);
+  all.insert(all.end(), cloud1, cloud1 + n_pairs);
+  HGS_TRY(ensure_index(h, all));
+  HGS_TRY(ensure_seed_grids(h, std::vector<hgs_cloud*>(cloud1, cloud1 + n_pairs)));
+  const size_t chunk = h->pair_chunk > 0 ? (size_t)h->pair_chunk : 65535;  // grid.y of one launch
+  out.clear();
+  out.reserve(n_pairs);
+  for (size_t p0 = 0; p0 < n_pairs; p0 += chunk) {
+    const size_t B = std::min(chunk, n_pairs - p0);
+    std::vector<TargetView> views(B);
+    for (size_t b = 0; b < B; b++) views[b] = target_view(cloud1[p0 + b]);
+    HGS_HIP(h, h->group_tviews.reserve(B * sizeof(TargetView)));
+    HGS_HIP(h, h->up.upload(h->group_tviews.p, views.data(), B * sizeof(TargetView), h->stream));
+    BatchShape s;
+    HGS_TRY(batch_shape(h, std::vector<hgs_cloud*>(cloud2 + p0, cloud2 + p0 + B), false, &s));
+    s.d_tviews = h->group_tviews.as<TargetView>();
+    std::vector<DevResult> poses(B);
+    std::memset(poses.data(), 0, B * sizeof(DevResult));
+    for (size_t b = 0; b < B; b++) std::memcpy(poses[b].T, relposes + 16 * (p0 + b), sizeof(float) * 16);
+    HGS_HIP(h, h->results.reserve(B * sizeof(DevResult)));
+    HGS_HIP(h, h->up.upload(h->results.p, poses.data(), B * sizeof(DevResult), h->stream));
+    HGS_HIP(h, h->partials_err.reserve(B * s.max_blocks * 2 * sizeof(double)));
+    BatchLane whole;  // every pair of the chunk on the engine's stream
+    whole.stream = h->stream, whole.B = (int)B, whole.partials_err = h->partials_err.as<double>();
+    lane_fitness(h, whole, s, max_range, false);
+    HGS_HIP(h, hipGetLastError());
+    std::vector<DevResult> r;
+    HGS_TRY(fetch_results(h, (int)B, r));
+    out.insert(out.end(), r.begin(), r.end());
+  }
+  return HGS_OK;
+}
+
 void to_public(const DevResult& d, int candidate, bool with_fitness, hgs_result* r) {
   std::memcpy(r->final_transformation, d.T, sizeof(float) * 16);
   r->converged = d.converged;
@@ -1367,6 +1442,7 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
   else if (k == "upload_trace") h->upload_trace = value != 0 ? 1 : 0;
   else if (k == "prefilter_fast") h->prefilter_fast = value != 0 ? 1 : 0;
   else if (k == "floor_chunk") h->floor_chunk = std::max(1, std::min(kFloorMaxChunk, value));
+  else if (k == "pair_chunk") h->pair_chunk = std::max(0, std::min(65535, value));                         // 0: what one launch holds
   else {
     h->err = "hgs_debug_set_option: unknown option '" + k + "'";
     return HGS_ERR_INVALID_ARGUMENT;
@@ -1652,6 +1728,27 @@ int hgs_calc_fitness_score(hgs_handle* h, hgs_cloud* cloud1, hgs_cloud* cloud2, 
   h->target = saved_t;
   if (rc != HGS_OK) return rc;
   *score = fitness_score(r[0]);
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+// Every edge of a graph update in one device batch (flush_keyframe_queue's odometry edges, hdl_graph_slam_nodelet.cpp:235, and the loop edges of :569).
+int hgs_calc_fitness_score_batch(hgs_handle* h, hgs_cloud* const* cloud1, hgs_cloud* const* cloud2, const float* relposes, size_t n_pairs, double max_range,
+                                 double* scores, uint32_t* num_inliers) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (n_pairs == 0) return HGS_OK;
+  if (!cloud1 || !cloud2 || !relposes || !scores) return HGS_ERR_INVALID_ARGUMENT;
+  for (size_t i = 0; i < n_pairs; i++)  // (an orphaned cloud has no owner)
+    if (!cloud1[i] || !cloud2[i] || cloud1[i]->owner != h || cloud2[i]->owner != h) return HGS_ERR_INVALID_ARGUMENT;
+  HGS_TRY(set_device(h));
+  std::vector<DevResult> r;
+  HGS_TRY(run_pair_fitness(h, cloud1, cloud2, relposes, n_pairs, max_range, r));
+  for (size_t i = 0; i < n_pairs; i++) {
+    scores[i] = fitness_score(r[i]);
+    if (num_inliers) num_inliers[i] = r[i].fit_count;
+  }
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
@@ -2904,6 +3001,27 @@ int hgs_debug_icp_step(hgs_handle* h, const double sums17[17], const double T12_
   for (int i = 0; i < 12; i++) T12_out[i] = st.x.m[i];
   flags3[0] = st.converged, flags3[1] = st.phase == ICP_DONE ? 1 : 0, flags3[2] = st.iterations;
   *mse = st.mse;
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_cloud_seed_grid(hgs_handle* h, hgs_cloud* cloud, uint32_t* tab, size_t cap, int32_t* bits, size_t* entries) try {
+  ApiLock lock(h);
+  if (!h || !cloud || cloud->owner != h || !entries || (cap > 0 && !tab)) return HGS_ERR_INVALID_ARGUMENT;
+  *entries = 0;
+  if (bits) *bits = 0;
+  if (!cloud->has_seed) return HGS_OK;
+  HGS_TRY(set_device(h));
+  const size_t n = seed_grid_entries(cloud->seed_bits), m = std::min(cap, n);
+  if (m > 0) {
+    HGS_HIP(h, h->h_xform.reserve(m * sizeof(uint32_t)));
+    HGS_HIP(h, hipMemcpyAsync(h->h_xform.p, cloud->seed_block.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HGS_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(tab, h->h_xform.p, m * sizeof(uint32_t));
+  }
+  *entries = n;
+  if (bits) *bits = cloud->seed_bits;
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);

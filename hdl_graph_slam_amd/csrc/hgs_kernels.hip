@@ -855,6 +855,58 @@ void launch_seed_grid_build(hipStream_t s, const float4* pts, const CloudMeta* m
   if (n_max <= 0) return;
   hipLaunchKernelGGL(k_seed_grid_build, dim3((n_max + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pts, meta, tab, bits);
 }
+// The seed grids of SEVERAL clouds in two launches (hgs_calc_fitness_score_batch: every new keyframe of a graph update is the tree side of its odometry
+// edge, hdl_graph_slam_nodelet.cpp:235): jobs[blockIdx.y] names one cloud's sorted points, meta record and table; blockIdx.x strides over that cloud's
+// table words (the clear) or points (the fill), and a block past its own job's size returns.  The job record is read block-uniformly in front of the
+// kernel's first store — scalar loads — and its pointers are declared global like problem_target's (no flat loads or stores).  The fill is
+// k_seed_grid_build's: the atomicMin of sorted positions makes every entry the smallest position that hashes there, whatever the launch shape, so a table
+// is word for word what the single-cloud kernel writes.
+template <typename T>
+__device__ __forceinline__ T* global_pointer_rw(T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
+#else
+  return p;
+#endif
+}
+__device__ __forceinline__ SeedGridJob seed_grid_job(const SeedGridJob* __restrict__ jobs, int j) {
+  SeedGridJob job = global_pointer(jobs)[j];
+  job.pts = global_pointer(job.pts), job.meta = global_pointer(job.meta), job.tab = global_pointer_rw(job.tab);
+  return job;
+}
+__global__ __launch_bounds__(kBlock) void k_seed_grid_clear_batch(const SeedGridJob* __restrict__ jobs) {
+  const SeedGridJob job = seed_grid_job(jobs, blockIdx.y);
+  const unsigned entries = (1u << job.bits) + (1u << (job.bits - 2)) + (1u << (job.bits - 4));  // seed_grid_entries
+  const unsigned first = blockIdx.x * kBlock;
+  if (first >= entries) return;
+  const unsigned step = gridDim.x * kBlock;
+  for (unsigned i = first + threadIdx.x; i < entries; i += step) job.tab[i] = 0xffffffffu;
+}
+__global__ __launch_bounds__(kBlock) void k_seed_grid_build_batch(const SeedGridJob* __restrict__ jobs) {
+  const SeedGridJob job = seed_grid_job(jobs, blockIdx.y);
+  const int n = job.meta->nvalid;
+  const int first = blockIdx.x * kBlock;
+  if (first >= n) return;
+  const int step = gridDim.x * kBlock;
+  for (int i = first + (int)threadIdx.x; i < n; i += step) {
+    const float4 p = job.pts[i];
+    int cx, cy, cz;
+    seed_cells(p.x, p.y, p.z, cx, cy, cz);
+    unsigned s0, s1, s2;
+    seed_slots(cx, cy, cz, job.bits, s0, s1, s2);
+    atomicMin(job.tab + s0, (unsigned)i);
+    atomicMin(job.tab + s1, (unsigned)i);
+    atomicMin(job.tab + s2, (unsigned)i);
+  }
+}
+// max_entries / max_n: the largest table and the largest cloud of the list (what grid.x is sized by; both kernels stride, so a cap only makes blocks loop)
+void launch_seed_grid_build_batch(hipStream_t s, const SeedGridJob* jobs, int njobs, size_t max_entries, int max_n) {
+  if (njobs <= 0) return;
+  const unsigned clear_x = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (max_entries + (size_t)kBlock * 8 - 1) / ((size_t)kBlock * 8)));
+  hipLaunchKernelGGL(k_seed_grid_clear_batch, dim3(clear_x, njobs), dim3(kBlock), 0, s, jobs);
+  const unsigned build_x = (unsigned)std::min(4096, std::max(1, (max_n + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(k_seed_grid_build_batch, dim3(build_x, njobs), dim3(kBlock), 0, s, jobs);
+}
 // the nearest of the (up to three) target points the grid holds for q's cells, or -1
 __device__ __forceinline__ int seed_grid_lookup(const TargetView& t, const F3& q) {
   int cx, cy, cz;

@@ -53,3 +53,14 @@ class InformationMatrixCalculator:
         if self.use_const_inf_matrix:
             return self.from_fitness_score(0.0)
         return self.from_fitness_score(reg.calc_fitness_score(cloud1, cloud2, relpose))
+
+    def calc_information_matrices(self, reg, edges) -> list:
+        """The information matrices of all edges of one graph update (the odometry edges of flush_keyframe_queue and the loop edges behind
+        it, apps/hdl_graph_slam_nodelet.cpp:235,569): `edges` is a list of (cloud1, cloud2, relpose).  One batched device call
+        (`RegistrationHIP.calc_fitness_scores` -> `hgs_calc_fitness_score_batch`), then `from_fitness_score` per edge; every matrix equals
+        calc_information_matrix of that edge.  use_const_inf_matrix touches no device."""
+        if self.use_const_inf_matrix:
+            return [self.from_fitness_score(0.0) for _ in edges]
+        if not edges:
+            return []
+        return [self.from_fitness_score(float(s)) for s in reg.calc_fitness_scores(list(edges))]

@@ -283,7 +283,30 @@ class RegistrationHIP:
         self._check(L.lib().hgs_calc_fitness_score(self._h, cloud1._h, cloud2._h, L.fptr(g), float(max_range), C.byref(score)))
         return score.value
 
+    def calc_fitness_scores(self, pairs, max_range: float = L.DBL_MAX, return_inliers: bool = False):
+        """Every edge of a graph update in one device batch (hgs_calc_fitness_score_batch; flush_keyframe_queue and the loop step,
+        apps/hdl_graph_slam_nodelet.cpp:235,569): `pairs` is a list of (cloud1, cloud2, relpose) — resident DeviceClouds, cloud1 the tree side.
+        Returns the scores as a float64 array, each the bits calc_fitness_score gives for that pair (with return_inliers: and the number of points
+        behind each mean, uint32)."""
+        n = len(pairs)
+        p1 = (C.c_void_p * max(n, 1))(*[p[0]._h for p in pairs])
+        p2 = (C.c_void_p * max(n, 1))(*[p[1]._h for p in pairs])
+        g = np.ascontiguousarray(np.stack([L.colmajor16(p[2]) for p in pairs]) if n else np.zeros((0, 16), np.float32))
+        scores, inliers = np.zeros(n, np.float64), np.zeros(n, np.uint32)
+        self._check(L.lib().hgs_calc_fitness_score_batch(self._h, p1, p2, g.ctypes.data_as(C.c_void_p), n, float(max_range),
+                                                         scores.ctypes.data_as(C.c_void_p), inliers.ctypes.data_as(C.c_void_p)))
+        return (scores, inliers) if return_inliers else scores
+
     # ---- stage-level hooks (parity tests)
+    def cloud_seed_grid(self, cloud: DeviceCloud):
+        """(table words as uint32, bits) of the cloud's seed grid; an empty array and 0 when it has none (hgs_debug_cloud_seed_grid)."""
+        bits, entries = C.c_int32(), C.c_size_t()
+        self._check(L.lib().hgs_debug_cloud_seed_grid(self._h, cloud._h, None, 0, C.byref(bits), C.byref(entries)))
+        tab = np.zeros(entries.value, np.uint32)
+        if entries.value:
+            self._check(L.lib().hgs_debug_cloud_seed_grid(self._h, cloud._h, tab.ctypes.data_as(C.c_void_p), entries.value, C.byref(bits), C.byref(entries)))
+        return tab, bits.value
+
     def nn_target(self, q_xyz):
         return self.getSearchMethodTarget().nearestKSearch(q_xyz, 1)
 

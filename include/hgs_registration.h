@@ -231,6 +231,18 @@ int hgs_loop_match_batch_sharded(hgs_handle* h, hgs_cloud* const* candidates, si
 
 /* ---- "next" row f1: InformationMatrixCalculator::calc_fitness_score (information_matrix_calculator.cpp:49-80) */
 int hgs_calc_fitness_score(hgs_handle* h, hgs_cloud* cloud1, hgs_cloud* cloud2, const float relpose[16], double max_range, double* score);
+/* All edges of one graph update in one device batch: flush_keyframe_queue adds up to max_keyframes_per_update odometry edges, each with the NEW keyframe
+ * as cloud1 (hdl_graph_slam_nodelet.cpp:235), and the loop step one edge per accepted loop (hdl_graph_slam_nodelet.cpp:569); each calls calc_fitness_score
+ * (information_matrix_calculator.cpp:49-80) on clouds too small to fill the device.  scores[i] is bit for bit what
+ * hgs_calc_fitness_score(h, cloud1[i], cloud2[i], relposes + 16 i, max_range, .) returns on a fresh engine holding the same clouds, num_inliers[i] the
+ * number of points behind that mean (0: the score is DBL_MAX).  A cloud may appear in any number of pairs and in either role (keyframe i is the tree of
+ * edge i and the query of edge i + 1); cloud1[i] == cloud2[i] is allowed.  Any hgs_method; the handle's target and source are neither read nor changed.
+ * The clouds' missing search indices are built in one pass and the missing seed grids of the cloud1s in two launches; more pairs than one launch holds
+ * run in chunks.  n_pairs == 0 returns HGS_OK.  HGS_ERR_INVALID_ARGUMENT, before anything is written or launched: a NULL array while n_pairs > 0, a NULL
+ * entry, a cloud of another handle, an orphaned cloud.  An additive symbol: HGS_ABI_VERSION is unchanged. */
+int hgs_calc_fitness_score_batch(hgs_handle* h, hgs_cloud* const* cloud1 /* n_pairs: the tree side */, hgs_cloud* const* cloud2 /* n_pairs: the query side */,
+                                 const float* relposes /* 16 floats per pair, column-major */, size_t n_pairs, double max_range,
+                                 double* scores /* n_pairs */, uint32_t* num_inliers /* n_pairs, NULL ok */);
 
 /* ---- "next" row f2: the prefilter in front of the path (apps/prefiltering_nodelet.cpp:131-182) -------------------- */
 enum hgs_downsample_method { HGS_DOWNSAMPLE_NONE = 0, HGS_DOWNSAMPLE_VOXELGRID = 1, HGS_DOWNSAMPLE_APPROX_VOXELGRID = 2 }; /* :51-72; pcl::VoxelGrid / pcl::ApproximateVoxelGrid */
@@ -385,7 +397,12 @@ int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3
  * of their covariances as stored (float: xx,xy,xz,yy,yz,zz) and the number of points.  *n_cells = voxels in the map; the first min(cap, *n_cells)
  * are written; any of the four arrays may be NULL.  An additive debug symbol: HGS_ABI_VERSION is unchanged (no struct or status code changed). */
 int hgs_debug_vgicp_voxels(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* cov6, int32_t* npts, int32_t* n_cells);
-/* One NDT derivative pass at p = (tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */
+/* The seed grid of a cloud (the three direct-mapped tables the 1-NN searches without correspondences start from, back to back): *entries = the number of
+ * 32-bit words of the grid, 0 when the cloud has none (never the tree side of a fitness pass, seed_grid = 0, invalidated); *bits (NULL ok) = log2 of the
+ * finest table's size; the first min(cap, *entries) words go to tab (NULL ok with cap 0).  A seed only bounds a search — a wrong table never changes a
+ * score — so the tables of hgs_calc_fitness_score_batch's batched build are tested by reading them.  An additive debug symbol. */
+int hgs_debug_cloud_seed_grid(hgs_handle* h, hgs_cloud* cloud, uint32_t* tab, size_t cap, int32_t* bits, size_t* entries);
+/* One NDT derivative pass at p =(tx,ty,tz,rx,ry,rz): score, gradient[6], Hessian[36]. */
 int hgs_debug_ndt_derivatives(hgs_handle* h, const double p6[6], double* score, double* g6, double* H36);
 /* the pure-host merge step of hgs_loop_match_batch_sharded: `gathered` = world blocks of `per` slots, of rank r's block the first
  * counts[r] carry records; fills all_out[0 .. n_total) (a candidate nobody reported: not converged, fitness DBL_MAX);
@@ -394,7 +411,7 @@ int hgs_debug_merge_shard_records(const hgs_result* gathered, const int32_t* cou
                                   hgs_result* all_out, int32_t* duplicate_id);
 /* A measurement / test knob of one engine: "batch_lanes", "lane_start", "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
  * "seed_grid", "knn_replay", "ndt_resident", "ndt_chunk", "hilbert_levels", "nn_qpw", "nn_qpw16_below", "nn_qpw32_below", "fused_rounds", "fused_rounds_below", "fused_rounds_max_problems", "fused_rounds_max_blocks", "early_result", "early_run_ahead",
- * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096).  Results never depend on them (the tests
+ * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "pair_chunk" (pairs per launch of hgs_calc_fitness_score_batch, 0 = 65535).  Results never depend on them (the tests
  * that force a code path check exactly that); A/B runs and those tests are the only callers — the library reads no tuning variable from the environment. */
 int hgs_debug_set_option(hgs_handle* h, const char* key, int32_t value);
 
