@@ -104,7 +104,7 @@ EXPORTS = [
     "hgs_cloud_create", "hgs_cloud_destroy", "hgs_cloud_size", "hgs_cloud_device_bytes", "hgs_cloud_invalidate",
     "hgs_set_target", "hgs_set_target_cloud", "hgs_set_source", "hgs_set_source_cloud",
     "hgs_align", "hgs_transform_source", "hgs_fitness", "hgs_nn_target",
-    "hgs_loop_match_batch", "hgs_loop_match_groups", "hgs_select_best", "hgs_calc_fitness_score", "hgs_calc_fitness_score_batch",
+    "hgs_loop_match_batch", "hgs_loop_match_groups", "hgs_align_pairs", "hgs_select_best", "hgs_calc_fitness_score", "hgs_calc_fitness_score_batch",
     "hgs_comm_get_unique_id", "hgs_comm_init", "hgs_comm_finalize", "hgs_loop_match_batch_sharded",
     "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_prefilter_framed", "hgs_cloud_download", "hgs_map_cloud_generate",
     "hgs_floor_params_default", "hgs_detect_floor", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts",
@@ -146,6 +146,7 @@ def lib():
     L.hgs_nn_target.argtypes = [vp, vp, sz, sz, vp, vp]
     L.hgs_loop_match_batch.argtypes = [vp, C.POINTER(vp), sz, vp, C.c_double, vp, C.POINTER(C.c_int32)]
     L.hgs_loop_match_groups.argtypes = [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), vp, C.c_double, vp, vp]
+    L.hgs_align_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(C.c_double), sz, vp]
     L.hgs_select_best.argtypes = [vp, sz, C.POINTER(C.c_int32)]
     L.hgs_comm_get_unique_id.argtypes = [vp]
     L.hgs_comm_init.argtypes = [vp, C.c_int32, C.c_int32, vp]

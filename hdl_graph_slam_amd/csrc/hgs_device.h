@@ -177,6 +177,9 @@ void launch_ndt_pack_hash(hipStream_t s, const int* keys, const int* vals, int2*
 // sorted: read the sources in Hilbert order (they have a search index); debug: only leave the totals in accum[].out
 void launch_ndt_pass(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
                      unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog);
+// ... with one target per problem, tviews[b] in HBM (hgs_align_pairs): the view and its grid box are reloaded where a block's run changes problem
+void launch_ndt_pass(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
+                     unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog);
 void launch_ndt_results(hipStream_t s, const CloudDesc* descs, const NdtState* states, DevResult* out, int B);
 
 void launch_vgicp_grid_params(hipStream_t s, CloudDesc desc, double resolution);
@@ -186,6 +189,11 @@ void launch_vgicp_build_cells(hipStream_t s, CloudDesc desc, const unsigned long
 void launch_vgicp_linearize(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c, double* partials,
                             int max_blocks, int B);
 void launch_vgicp_error(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c, double* partials_err,
+                        int max_blocks, int B);
+// ... with one voxel map per problem, tviews[b] in HBM (hgs_align_pairs)
+void launch_vgicp_linearize(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c, double* partials,
+                            int max_blocks, int B);
+void launch_vgicp_error(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c, double* partials_err,
                         int max_blocks, int B);
 
 // map cloud (src/hdl_graph_slam/map_cloud_generator.cpp)

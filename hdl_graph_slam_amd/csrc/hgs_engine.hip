@@ -147,6 +147,7 @@ struct hgs_handle {
   DeviceBuffer lane_partials[7], lane_partials_err[7];
   DeviceBuffer ndt_accum;  // NdtAccum per problem of the running NDT batch
   DeviceBuffer group_tviews, group_corr;  // hgs_loop_match_groups: one TargetView and one correspondence scratch per problem (run_group_batch)
+  DeviceBuffer group_vviews;              // hgs_align_pairs, NDT_OMP / FAST_VGICP: one NdtTargetView per problem (run_pair_batch)
   DeviceBuffer seed_jobs;                 // ensure_seed_grids: one SeedGridJob per cloud of the list
   int pair_chunk = 0;                     // hgs_calc_fitness_score_batch: pairs per launch (0: what grid.y holds, 65535); the results do not depend on it (tests)
   hgs::Comm* comm = nullptr;            // hgs_comm_init: the ranks of a sharded loop-closure batch
@@ -912,6 +913,7 @@ struct BatchShape {
   int max_blocks, err_blocks;         // rows of the partial-sum buffers / blocks of the 256-point kernels, per problem
   const CloudDesc* d_descs;           // the sources' descriptors on the device
   const TargetView* d_tviews;         // one target per problem, on the device (run_group_batch); null: every problem against the handle's target
+  const NdtTargetView* d_vviews;      // ... and its voxel table (run_pair_batch: NDT_OMP, FAST_VGICP); null: the handle's target's
 };
 
 // launch(target): with the lane's slice of the per-problem views, or with the one view `tv` by value — the two families of instantiations of the point kernels
@@ -924,7 +926,7 @@ void with_lane_target(const BatchShape& s, const BatchLane& L, const TargetView&
 // lm_rounds: the batch iterates (run_batch); false: a fitness pass alone (run_fitness), which has no two-launch rounds to size for
 int batch_shape(hgs_handle* h, const std::vector<hgs_cloud*>& sources, bool lm_rounds, BatchShape* out, int* const* corr_of = nullptr) {
   BatchShape& s = *out;
-  s.d_tviews = nullptr;
+  s.d_tviews = nullptr, s.d_vviews = nullptr;
   s.B = (int)sources.size();
   s.max_n = 0;
   for (hgs_cloud* c : sources) s.max_n = std::max(s.max_n, (int)c->n_input);
@@ -984,8 +986,8 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
   HGS_HIP(h, h->states.reserve((size_t)B * sizeof(GicpState) * (round2 ? 2 : 1)));
   GicpState* st = h->states.as<GicpState>();
   GicpState* st_other = st + B;
-  const TargetView tv = s.d_tviews ? TargetView{} : target_view(tgt);  // (run_group_batch: the views are on the device, the handle's target plays no part)
-  const NdtTargetView vtv = voxel ? vgicp_target_view(tgt) : NdtTargetView{};
+  const TargetView tv = s.d_tviews || s.d_vviews ? TargetView{} : target_view(tgt);  // (run_group_batch, run_pair_batch: the views are on the device, the handle's target plays no part)
+  const NdtTargetView vtv = voxel && !s.d_vviews ? vgicp_target_view(tgt) : NdtTargetView{};  // (run_pair_batch: one voxel map per problem, on the device)
   const long max_rounds = (long)std::max(1, c.max_iterations) * std::max(1, c.lm_max_iterations) + 2 + (round2 ? 1 : 0);  // (round2: a round's accept / reject runs in the next round's first kernel)
   std::vector<BatchLane> lanes;
   HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccNdt * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
@@ -1019,7 +1021,8 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
     }
     {
       StageTimer tm(h, HGS_STAGE_LINEARIZE);
-      if (voxel) launch_vgicp_linearize(L.stream, dd, vtv, ls, vc, L.partials, max_blocks, L.B);
+      if (voxel && s.d_vviews) launch_vgicp_linearize(L.stream, dd, s.d_vviews + L.b0, ls, vc, L.partials, max_blocks, L.B);
+      else if (voxel) launch_vgicp_linearize(L.stream, dd, vtv, ls, vc, L.partials, max_blocks, L.B);
       else with_lane_target(s, L, tv, [&](auto t) { launch_gicp_linearize(L.stream, dd, t, ls, c, L.partials, max_blocks, L.B, s.qpw); });
     }
     {
@@ -1028,7 +1031,8 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
     }
     {
       StageTimer tm(h, HGS_STAGE_ERROR);
-      if (voxel) launch_vgicp_error(L.stream, dd, vtv, ls, vc, L.partials_err, max_blocks, L.B);
+      if (voxel && s.d_vviews) launch_vgicp_error(L.stream, dd, s.d_vviews + L.b0, ls, vc, L.partials_err, max_blocks, L.B);
+      else if (voxel) launch_vgicp_error(L.stream, dd, vtv, ls, vc, L.partials_err, max_blocks, L.B);
       else with_lane_target(s, L, tv, [&](auto t) { launch_gicp_error(L.stream, dd, t, ls, L.partials_err, max_blocks, L.B); });
     }
     {
@@ -1135,7 +1139,7 @@ int run_ndt_rounds(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const 
   HGS_HIP(h, h->angles.reserve((size_t)B * sizeof(NdtAngles)));
   NdtState* st = h->states.as<NdtState>();
   NdtAngles* ang = h->angles.as<NdtAngles>();
-  const NdtTargetView tv = ndt_target_view(h, h->target);
+  const NdtTargetView tv = s.d_vviews ? NdtTargetView{} : ndt_target_view(h, h->target);  // (run_pair_batch: the views are on the device)
   // the sums are order-independent (hgs_ndt.h): read the sources in Hilbert order whenever they have a search index
   // (neighbouring lanes then share cells), in input order otherwise
   if (h->ndt_sort == 1) HGS_TRY(ensure_index(h, sources));
@@ -1157,8 +1161,12 @@ int run_ndt_rounds(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const 
   drive_lanes(lanes, max_rounds, [&](BatchLane& L) {
     StageTimer tm(h, HGS_STAGE_LINEARIZE);
     const NdtLanePlan& P = plans[&L - lanes.data()];
-    launch_ndt_pass(L.stream, s.d_descs + L.b0, tv, st + L.b0, ang + L.b0, c, accum + L.b0, P.tile_base, P.queues, L.B, (int)(L.round & 1), P.blocks, P.chunk,
-                    sorted ? 1 : 0, 0, L.prog);
+    if (s.d_vviews)  // the lane's slice: a block's items are numbered within the lane, and so are the views it reloads (k_ndt_pass)
+      launch_ndt_pass(L.stream, s.d_descs + L.b0, s.d_vviews + L.b0, st + L.b0, ang + L.b0, c, accum + L.b0, P.tile_base, P.queues, L.B, (int)(L.round & 1), P.blocks,
+                      P.chunk, sorted ? 1 : 0, 0, L.prog);
+    else
+      launch_ndt_pass(L.stream, s.d_descs + L.b0, tv, st + L.b0, ang + L.b0, c, accum + L.b0, P.tile_base, P.queues, L.B, (int)(L.round & 1), P.blocks, P.chunk,
+                      sorted ? 1 : 0, 0, L.prog);
   }, finish_lane);
   return close_lanes(h, lanes);
 }
@@ -1214,7 +1222,8 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
 //     bounds the walk (k_gicp_linearize), so a record equals the one a batch against that target alone gives, bit for bit;
 //   * neither h->target nor h->source is read or written.
 // FAST_GICP and ICP only (the caller has checked): their targets are a search index (+ covariances), which every cloud of the union gets in one ensure_* pass.
-int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const std::vector<hgs_cloud*>& sources, const float* guesses_host, double max_range) {
+// fit_max_range null (hgs_align_pairs without a fitness pass): the registrations alone.
+int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const std::vector<hgs_cloud*>& sources, const float* guesses_host, const double* fit_max_range) {
   const int B = (int)sources.size();
   const int method = h->prm.method;
   h->early_valid = false;
@@ -1222,7 +1231,7 @@ int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const
   all.insert(all.end(), targets.begin(), targets.end());
   if (method == HGS_FAST_GICP) HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
   else HGS_TRY(ensure_index(h, all));
-  if (method != HGS_FAST_GICP)  // as run_batch: the fitness pass of a point without a correspondence starts from the target's seed grid
+  if (fit_max_range && method != HGS_FAST_GICP)  // as run_batch: the fitness pass of a point without a correspondence starts from the target's seed grid
     for (hgs_cloud* t : targets) HGS_TRY(ensure_seed_grid(h, t));
   // the correspondence scratch of problem b: as many entries as the source's own corr[] (its padded point count), 256-byte aligned
   std::vector<size_t> corr_off(B + 1, 0);
@@ -1243,8 +1252,78 @@ int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const
   HGS_HIP(h, h->results.reserve((size_t)B * sizeof(DevResult)));
   HGS_HIP(h, h->partials.reserve((size_t)B * s.max_blocks * kAccNdt * sizeof(double)));
   HGS_HIP(h, h->partials_err.reserve((size_t)B * s.max_blocks * 2 * sizeof(double)));
-  if (method == HGS_FAST_GICP) HGS_TRY(run_gicp_rounds(h, s, guesses_host, false, &max_range));
-  else HGS_TRY(run_icp_rounds(h, s, &max_range));
+  if (method == HGS_FAST_GICP) HGS_TRY(run_gicp_rounds(h, s, guesses_host, false, fit_max_range));
+  else HGS_TRY(run_icp_rounds(h, s, fit_max_range));
+  HGS_HIP(h, hipGetLastError());
+  return HGS_OK;
+}
+
+// hgs_align_pairs: problem b registers sources[b] against targets[b] from its own guess, all problems in ONE batch, with getFitnessScore(*fit_max_range)
+// behind each on request.  FAST_GICP and ICP: run_group_batch.  NDT_OMP and FAST_VGICP: their targets are voxel tables, cached on the cloud —
+//   * one ensure_* pass over the union of the clouds (FAST_VGICP: covariances; a fitness pass: search indices and the targets' seed grids), one table build
+//     per distinct target that lacks one;
+//   * one NdtTargetView per problem in a device array (h->group_vviews), read by the const NdtTargetView* instantiations of k_ndt_pass /
+//     k_vgicp_linearize / k_vgicp_error; the fitness pass reads h->group_tviews as in run_group_batch;
+//   * FAST_VGICP keeps a point's voxel hit count in corr[] between its two kernels, so every problem gets its own scratch as in run_group_batch (a cloud
+//     may be the source of several problems); NDT_OMP reads and writes no corr[];
+//   * lanes, lane plans and launch shapes are chosen on the whole problem list as for a batch against one target: a lane boundary may fall anywhere;
+//   * neither h->target nor h->source is read or written.
+int run_pair_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const std::vector<hgs_cloud*>& sources, const float* guesses_host, const double* fit_max_range) {
+  const int method = h->prm.method;
+  if (method == HGS_FAST_GICP || method == HGS_ICP) return run_group_batch(h, targets, sources, guesses_host, fit_max_range);
+  const int B = (int)sources.size();
+  const bool voxel = method == HGS_FAST_VGICP;
+  h->early_valid = false;
+  std::vector<hgs_cloud*> all(sources);
+  all.insert(all.end(), targets.begin(), targets.end());
+  std::vector<hgs_cloud*> distinct;  // targets, in order of first appearance
+  for (hgs_cloud* t : targets)
+    if (std::find(distinct.begin(), distinct.end(), t) == distinct.end()) distinct.push_back(t);
+  if (fit_max_range) HGS_TRY(ensure_index(h, all));
+  if (voxel) {
+    HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
+    for (hgs_cloud* t : distinct) {
+      const int rc = ensure_vgicp_target(h, t);
+      if (rc == HGS_ERR_UNSUPPORTED) {  // (vgicp_grid_too_large has described the grid: say which pair it belongs to)
+        const size_t pair = (size_t)(std::find(targets.begin(), targets.end(), t) - targets.begin());
+        h->err = "hgs_align_pairs: pair " + std::to_string(pair) + ": " + h->err;
+      }
+      HGS_TRY(rc);
+    }
+  } else {
+    for (hgs_cloud* t : distinct) HGS_TRY(ensure_ndt_target(h, t));
+  }
+  if (fit_max_range) HGS_TRY(ensure_seed_grids(h, distinct));
+  std::vector<int*> corr_of;
+  if (voxel) {
+    std::vector<size_t> corr_off(B + 1, 0);
+    for (int b = 0; b < B; b++) corr_off[b + 1] = corr_off[b] + align_up((size_t)sources[b]->P * kLeaf, 64);
+    HGS_HIP(h, h->group_corr.reserve(std::max<size_t>(1, corr_off[B]) * sizeof(int)));
+    HGS_HIP(h, hipMemsetAsync(h->group_corr.p, 0xff, corr_off[B] * sizeof(int), h->stream));
+    corr_of.resize(B);
+    for (int b = 0; b < B; b++) corr_of[b] = h->group_corr.as<int>() + corr_off[b];
+  }
+  std::vector<NdtTargetView> vviews(B);
+  for (int b = 0; b < B; b++) vviews[b] = voxel ? vgicp_target_view(targets[b]) : ndt_target_view(h, targets[b]);
+  HGS_HIP(h, h->group_vviews.reserve((size_t)B * sizeof(NdtTargetView)));
+  HGS_HIP(h, h->up.upload(h->group_vviews.p, vviews.data(), (size_t)B * sizeof(NdtTargetView), h->stream));
+  if (fit_max_range) {
+    std::vector<TargetView> views(B);
+    for (int b = 0; b < B; b++) views[b] = target_view(targets[b]);
+    HGS_HIP(h, h->group_tviews.reserve((size_t)B * sizeof(TargetView)));
+    HGS_HIP(h, h->up.upload(h->group_tviews.p, views.data(), (size_t)B * sizeof(TargetView), h->stream));
+  }
+  BatchShape s;
+  HGS_TRY(batch_shape(h, sources, true, &s, voxel ? corr_of.data() : nullptr));
+  s.d_vviews = h->group_vviews.as<NdtTargetView>();
+  s.d_tviews = fit_max_range ? h->group_tviews.as<TargetView>() : nullptr;
+  HGS_HIP(h, h->guesses.reserve((size_t)B * 16 * sizeof(float)));
+  HGS_HIP(h, h->up.upload(h->guesses.p, guesses_host, (size_t)B * 16 * sizeof(float), h->stream));
+  HGS_HIP(h, h->results.reserve((size_t)B * sizeof(DevResult)));
+  HGS_HIP(h, h->partials.reserve((size_t)B * s.max_blocks * kAccNdt * sizeof(double)));
+  HGS_HIP(h, h->partials_err.reserve((size_t)B * s.max_blocks * 2 * sizeof(double)));
+  if (voxel) HGS_TRY(run_gicp_rounds(h, s, guesses_host, false, fit_max_range));
+  else HGS_TRY(run_ndt_rounds(h, sources, s, fit_max_range));
   HGS_HIP(h, hipGetLastError());
   return HGS_OK;
 }
@@ -1867,7 +1946,7 @@ int hgs_loop_match_groups(hgs_handle* h, hgs_cloud* const* targets, size_t n_gro
   }
   if (n == 0) return HGS_OK;
   HGS_TRY(set_device(h));
-  HGS_TRY(run_group_batch(h, tgt, src, guesses, max_range));
+  HGS_TRY(run_group_batch(h, tgt, src, guesses, &max_range));
   std::vector<DevResult> r;
   HGS_TRY(fetch_results(h, (int)n, r));
   for (size_t g = 0; g < n_groups; g++) {
@@ -1875,6 +1954,29 @@ int hgs_loop_match_groups(hgs_handle* h, hgs_cloud* const* targets, size_t n_gro
     for (size_t i = g0; i < g1; i++) to_public(r[i], (int)(i - g0), true, &out[i]);
     if (best && g1 > g0) HGS_TRY(hgs_select_best(out + g0, g1 - g0, &best[g]));
   }
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+// n independent registrations in one batch, every engine: the primitive under the grouped call (repeat the target, select per group) and under several
+// odometry streams in lock-step (one pair per sensor).
+int hgs_align_pairs(hgs_handle* h, hgs_cloud* const* targets, hgs_cloud* const* sources, const float* guesses, const double* max_range, size_t n,
+                    hgs_result* out) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return HGS_OK;
+  if (n > (size_t)INT_MAX || !targets || !sources || !guesses || !out) return HGS_ERR_INVALID_ARGUMENT;
+  std::vector<hgs_cloud*> tgt(targets, targets + n), src(sources, sources + n);
+  for (size_t i = 0; i < n; i++)
+    if (!tgt[i] || !src[i] || tgt[i]->owner != h || src[i]->owner != h) return HGS_ERR_INVALID_ARGUMENT;
+  HGS_TRY(set_device(h));
+  HGS_TRY(run_pair_batch(h, tgt, src, guesses, max_range));
+  std::vector<DevResult> r;
+  if (h->early_valid) r.assign(1, *h->h_early.as<DevResult>());  // (one FAST_GICP pair without a fitness pass: handed over as hgs_align's result is)
+  else HGS_TRY(fetch_results(h, (int)n, r));
+  h->early_valid = false;
+  for (size_t i = 0; i < n; i++) to_public(r[i], (int)i, max_range != nullptr, &out[i]);
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);

@@ -15,6 +15,7 @@
 // (hgs_wave_bvh.h), the per-point algebra by HBM: no MFMA (the contraction is 6x6), coalesced float4 loads, wave64
 // shuffle reductions, deterministic two-stage sums.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/hgs_registration.h"
 #include "hgs_device.h"
 #include "hgs_wave_bvh.h"
@@ -1791,6 +1792,46 @@ __device__ __forceinline__ int ndt_front_key(const F3& xt, int have, const NdtTa
   return in ? (px - g.mnx) + (py - g.mny) * g.mul1 + (pz - g.mnz) * g.mul2 : -1;
 }
 
+// k_ndt_pass's target: the launch's (by value), or problem b's record and grid box read from tviews[b] (hgs_align_pairs).  That read happens in the
+// middle of the pass, behind stores and atomics, where the compiler no longer issues a scalar load for a uniform address by itself; b is block-uniform
+// by construction (every lane follows the same items), so every dword goes through v_readfirstlane and the view and the box stay in scalar registers as
+// the by-value form's do (the kernel is at 256 VGPRs).  The record's pointers are declared global like problem_target's: no flat loads in the probes.
+__device__ __forceinline__ int uniform_word(const int* p) { return __builtin_amdgcn_readfirstlane(*global_pointer(p)); }
+__device__ __forceinline__ NdtGridBox ndt_grid_box(const CloudMeta* m) {
+  return {m->ndt_min_b[0], m->ndt_min_b[1], m->ndt_min_b[2], m->ndt_max_b[0], m->ndt_max_b[1], m->ndt_max_b[2], m->ndt_div_mul[1], m->ndt_div_mul[2]};
+}
+template <typename TGT>
+struct NdtPassTarget;
+template <>
+struct NdtPassTarget<NdtTargetView> {  // the kernel argument itself and its box, read once
+  const NdtTargetView& tgt;
+  const NdtGridBox box;
+  __device__ __forceinline__ explicit NdtPassTarget(const NdtTargetView& t) : tgt(t), box(ndt_grid_box(t.meta)) {}
+  __device__ __forceinline__ void enter_problem(const NdtTargetView&, int) {}
+};
+template <>
+struct NdtPassTarget<const NdtTargetView*> {  // (nothing until the first item: a block's first item always changes problem)
+  NdtTargetView tgt;
+  NdtGridBox box;
+  __device__ __forceinline__ explicit NdtPassTarget(const NdtTargetView*) : tgt{}, box{} {}
+  __device__ __forceinline__ void enter_problem(const NdtTargetView* __restrict__ tviews, int b) {
+    static_assert(sizeof(NdtTargetView) % sizeof(int) == 0, "read word by word");
+    union {
+      NdtTargetView v;
+      int w[sizeof(NdtTargetView) / sizeof(int)];
+    } u;
+    const int* rec = reinterpret_cast<const int*>(tviews + __builtin_amdgcn_readfirstlane(b));
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(NdtTargetView) / sizeof(int)); k++) u.w[k] = uniform_word(rec + k);
+    tgt = u.v;
+    tgt.hash_keys = global_pointer(tgt.hash_keys), tgt.hash_vals = global_pointer(tgt.hash_vals), tgt.cells = global_pointer(tgt.cells);
+    tgt.meta = global_pointer(tgt.meta), tgt.hash_kv = global_pointer(tgt.hash_kv);
+    const CloudMeta* m = tgt.meta;
+    box = {uniform_word(&m->ndt_min_b[0]), uniform_word(&m->ndt_min_b[1]), uniform_word(&m->ndt_min_b[2]), uniform_word(&m->ndt_max_b[0]),
+           uniform_word(&m->ndt_max_b[1]), uniform_word(&m->ndt_max_b[2]), uniform_word(&m->ndt_div_mul[1]), uniform_word(&m->ndt_div_mul[2])};
+  }
+};
+
 // x: the lane's source point; have: the lane has one
 __device__ __forceinline__ void ndt_front_load(float4& x, int& have, const CloudDesc& d, int sorted, int i, int n) {
   have = i < n ? 1 : 0;
@@ -1986,8 +2027,14 @@ __device__ __noinline__ bool ndt_flush(NdtPassShared& S, NdtAccum& A, int tiles,
   return S.last != 0;
 }
 
-template <int NOFF>
-__global__ __launch_bounds__(kBlock, 2) void k_ndt_pass(const CloudDesc* __restrict__ descs, NdtTargetView tgt, NdtState* states, NdtAngles* angles, NdtConsts c,
+// The target of a pass (template parameter TGT).  NdtTargetView: the launch's one target, by value in the kernel arguments (hgs_align,
+// hgs_loop_match_batch).  const NdtTargetView*: one view per problem in HBM (hgs_align_pairs).  Here the problem is not blockIdx.y: a block pulls
+// (problem, tile) items from the lane's queue and changes problem inside its run, so in the per-problem form the view and the grid box built from its
+// meta record are part of "the problem being worked on" and are reloaded where cur_b changes, next to d = descs[cur_b].  The staged prefetch of the
+// next tile never crosses a problem boundary (stage_next requires item + 1 < cur_end): a staged tile always belongs to the current target.
+// Two instantiations of one text, no run-time branch: the by-value form is instruction for instruction what it was before the other existed.
+template <int NOFF, typename TGT = NdtTargetView>
+__global__ __launch_bounds__(kBlock, 2) void k_ndt_pass(const CloudDesc* __restrict__ descs, TGT tgt_arg, NdtState* states, NdtAngles* angles, NdtConsts c,
                                                          NdtAccum* accum, const int* __restrict__ tile_base /* [B + 1] */, unsigned long long* queues /* [2] */, int B,
                                                          int parity, int chunk, int sorted, int debug, Progress prog) {
   __shared__ NdtPassShared S;
@@ -2009,8 +2056,9 @@ __global__ __launch_bounds__(kBlock, 2) void k_ndt_pass(const CloudDesc* __restr
   const int static_items = (int)gridDim.x * first_chunk;
   if (threadIdx.x == 0) S.out_of_range = 0, S.adds = 0, S.next = (int)blockIdx.x * first_chunk, S.next_chunk = first_chunk, S.consts = c, S.prog = prog, S.debug = debug;
   __syncthreads();
-  const CloudMeta* m = tgt.meta;
-  const NdtGridBox box = {m->ndt_min_b[0], m->ndt_min_b[1], m->ndt_min_b[2], m->ndt_max_b[0], m->ndt_max_b[1], m->ndt_max_b[2], m->ndt_div_mul[1], m->ndt_div_mul[2]};
+  NdtPassTarget<TGT> cur(tgt_arg);
+  const NdtTargetView& tgt = cur.tgt;
+  const NdtGridBox& box = cur.box;
   const float d1 = (float)c.gauss_d1, d2 = (float)c.gauss_d2;
   // The tile at hand: point, transformed point, first hash probes, cell indices; `staged`: filled during the previous tile's reduction.
   // Not for the 27-cell neighbourhood, whose 27 probes in flight do not fit the register file next to the 43 sums.
@@ -2053,6 +2101,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_ndt_pass(const CloudDesc* __restr
         if (cur_active) {
           d = descs[cur_b];
           cur_n = sorted ? d.meta->nvalid : d.n_input;
+          cur.enter_problem(tgt_arg, cur_b);
           __syncthreads();
           for (int k = threadIdx.x; k < (int)(sizeof(NdtAngles) / 4); k += kBlock) {  // j[8][3] | h[15][3] | T[12] -> NdtAnglesLds
             const float v = reinterpret_cast<const float*>(&angles[cur_b])[k];
@@ -2145,14 +2194,23 @@ __global__ __launch_bounds__(kBlock, 2) void k_ndt_pass(const CloudDesc* __restr
   if (cur_b >= 0 && cur_active && ndt_flush(S, accum[cur_b], cur_tiles, tile_base[cur_b + 1] - tile_base[cur_b]))
     ndt_finish_problem(S, accum[cur_b], states[cur_b], angles[cur_b]);
 }
-void launch_ndt_pass(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
-                     unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog) {
+template <typename TGT>
+static void launch_ndt_pass_for(hipStream_t s, const CloudDesc* descs, TGT tgt, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
+                                unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog) {
   const dim3 grid(blocks < 1 ? 1 : blocks), block(kBlock);
   if (chunk < 1) chunk = 1;
   parity &= 1;
-  if (c.search == 1) hipLaunchKernelGGL(k_ndt_pass<1>, grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
-  else if (c.search == 2) hipLaunchKernelGGL(k_ndt_pass<7>, grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
-  else hipLaunchKernelGGL(k_ndt_pass<27>, grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
+  if (c.search == 1) hipLaunchKernelGGL((k_ndt_pass<1, TGT>), grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
+  else if (c.search == 2) hipLaunchKernelGGL((k_ndt_pass<7, TGT>), grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
+  else hipLaunchKernelGGL((k_ndt_pass<27, TGT>), grid, block, 0, s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, chunk, sorted, debug, prog);
+}
+void launch_ndt_pass(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
+                     unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog) {
+  launch_ndt_pass_for<NdtTargetView>(s, descs, tgt, states, angles, c, accum, tile_base, queues, B, parity, blocks, chunk, sorted, debug, prog);
+}
+void launch_ndt_pass(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, NdtState* states, NdtAngles* angles, NdtConsts c, NdtAccum* accum, const int* tile_base,
+                     unsigned long long* queues, int B, int parity, int blocks, int chunk, int sorted, int debug, Progress prog) {
+  launch_ndt_pass_for<const NdtTargetView*>(s, descs, tviews, states, angles, c, accum, tile_base, queues, B, parity, blocks, chunk, sorted, debug, prog);
 }
 
 __global__ void k_ndt_results(const CloudDesc* descs, const NdtState* states, DevResult* out, int B) {
@@ -2264,9 +2322,23 @@ __device__ __forceinline__ NdtGrid vgicp_grid_of(const NdtTargetView& tgt) {
 
 // update_correspondences + linearize of FastVGICP fused.  Algorithmic bytes per source point (DIRECT1):
 // 16 (a_i) + 24 (C_A) + 40 (voxel: mean 12, cov 24, n 4) = 80; the voxel table of a LiDAR scan is L2-resident.
-__global__ __launch_bounds__(kBlock) void k_vgicp_linearize(const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c,
-                                                            double* __restrict__ partials, int max_blocks) {
+// TGT: the launch's one voxel map by value, or one view per problem in HBM (hgs_align_pairs) — problem_target's rule for the point kernels: tviews[b] is
+// read in front of the kernel's first store (scalar loads), its pointers declared global (the table probes stay global_load).  The two forms are two
+// instantiations of one body, each behind a plain kernel that owns the block's LDS array.  (next to its per-problem twin the
+// by-value k_vgicp_linearize compiles to one more address instruction in block_reduce_store whatever the form — template kernel, this one, or the old
+// kernel left word for word — and in this form to eight v_add_f64 with their operands swapped; its results are the same bits.)
+__device__ __forceinline__ const NdtTargetView& problem_target(const NdtTargetView& t, int) { return t; }
+__device__ __forceinline__ NdtTargetView problem_target(const NdtTargetView* __restrict__ tviews, int b) {
+  NdtTargetView t = global_pointer(tviews)[b];
+  t.hash_keys = global_pointer(t.hash_keys), t.hash_vals = global_pointer(t.hash_vals), t.cells = global_pointer(t.cells);
+  t.meta = global_pointer(t.meta), t.hash_kv = global_pointer(t.hash_kv);
+  return t;
+}
+template <typename TGT>
+__device__ __forceinline__ void vgicp_linearize_block(const CloudDesc* descs, const TGT& tgt_arg, const GicpState* states, const VgicpConsts& c,
+                                                      double* __restrict__ partials, int max_blocks, double* lds /* [4 * kAcc] */) {
   const int b = blockIdx.y;
+  const NdtTargetView& tgt = problem_target(tgt_arg, b);
   if (states[b].phase != GICP_LINEARIZE) return;
   const CloudDesc d = descs[b];
   const int n = d.meta->nvalid;
@@ -2274,7 +2346,6 @@ __global__ __launch_bounds__(kBlock) void k_vgicp_linearize(const CloudDesc* des
   if ((int)blockIdx.x >= ntiles) return;
   const int tile = (int)blockIdx.x;
   const int i = tile * kBlock + threadIdx.x;
-  __shared__ double lds[4 * kAcc];
   double acc[kAcc];
 #pragma unroll
   for (int k = 0; k < kAcc; k++) acc[k] = 0.0;
@@ -2288,15 +2359,31 @@ __global__ __launch_bounds__(kBlock) void k_vgicp_linearize(const CloudDesc* des
   }
   block_reduce_store<kAcc>(acc, partials + ((size_t)b * max_blocks + tile) * kAcc, lds);
 }
+__global__ __launch_bounds__(kBlock) void k_vgicp_linearize(const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c,
+                                                            double* __restrict__ partials, int max_blocks) {
+  __shared__ double lds[4 * kAcc];
+  vgicp_linearize_block(descs, tgt, states, c, partials, max_blocks, lds);
+}
+__global__ __launch_bounds__(kBlock) void k_vgicp_linearize_pairs(const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c,
+                                                                  double* __restrict__ partials, int max_blocks) {
+  __shared__ double lds[4 * kAcc];
+  vgicp_linearize_block(descs, tviews, states, c, partials, max_blocks, lds);
+}
 void launch_vgicp_linearize(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c, double* partials,
                             int max_blocks, int B) {
   hipLaunchKernelGGL(k_vgicp_linearize, dim3(max_blocks, B), dim3(kBlock), 0, s, descs, tgt, states, c, partials, max_blocks);
 }
+void launch_vgicp_linearize(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c, double* partials,
+                            int max_blocks, int B) {
+  hipLaunchKernelGGL(k_vgicp_linearize_pairs, dim3(max_blocks, B), dim3(kBlock), 0, s, descs, tviews, states, c, partials, max_blocks);
+}
 
 // compute_error(xi): voxels and Mahalanobis matrices of the linearisation pose x0, residuals at the LM trial pose xi.
-__global__ __launch_bounds__(kBlock) void k_vgicp_error(const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c,
-                                                        double* __restrict__ partials_err, int max_blocks) {
+template <typename TGT>
+__device__ __forceinline__ void vgicp_error_block(const CloudDesc* descs, const TGT& tgt_arg, const GicpState* states, const VgicpConsts& c,
+                                                  double* __restrict__ partials_err, int max_blocks, double* lds /* [4] */) {
   const int b = blockIdx.y;
+  const NdtTargetView& tgt = problem_target(tgt_arg, b);
   if (states[b].phase != GICP_TRY) return;
   const CloudDesc d = descs[b];
   const int n = d.meta->nvalid;
@@ -2304,7 +2391,6 @@ __global__ __launch_bounds__(kBlock) void k_vgicp_error(const CloudDesc* descs, 
   if ((int)blockIdx.x >= ntiles) return;
   const int tile = (int)blockIdx.x;
   const int i = tile * kBlock + threadIdx.x;
-  __shared__ double lds[4];
   double err = 0.0;
   if (i < n && d.corr[i] > 0) {
     const NdtGrid g = vgicp_grid_of(tgt);
@@ -2313,9 +2399,23 @@ __global__ __launch_bounds__(kBlock) void k_vgicp_error(const CloudDesc* descs, 
   }
   block_reduce_store<1>(&err, partials_err + (size_t)b * max_blocks + tile, lds);
 }
+__global__ __launch_bounds__(kBlock) void k_vgicp_error(const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c,
+                                                        double* __restrict__ partials_err, int max_blocks) {
+  __shared__ double lds[4];
+  vgicp_error_block(descs, tgt, states, c, partials_err, max_blocks, lds);
+}
+__global__ __launch_bounds__(kBlock) void k_vgicp_error_pairs(const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c,
+                                                              double* __restrict__ partials_err, int max_blocks) {
+  __shared__ double lds[4];
+  vgicp_error_block(descs, tviews, states, c, partials_err, max_blocks, lds);
+}
 void launch_vgicp_error(hipStream_t s, const CloudDesc* descs, NdtTargetView tgt, const GicpState* states, VgicpConsts c, double* partials_err,
                         int max_blocks, int B) {
   hipLaunchKernelGGL(k_vgicp_error, dim3(max_blocks, B), dim3(kBlock), 0, s, descs, tgt, states, c, partials_err, max_blocks);
+}
+void launch_vgicp_error(hipStream_t s, const CloudDesc* descs, const NdtTargetView* tviews, const GicpState* states, VgicpConsts c, double* partials_err,
+                        int max_blocks, int B) {
+  hipLaunchKernelGGL(k_vgicp_error_pairs, dim3(max_blocks, B), dim3(kBlock), 0, s, descs, tviews, states, c, partials_err, max_blocks);
 }
 
 // ------------------------------------------------------------------------------------------------ prefilter (next row f2)

@@ -10,6 +10,9 @@ Semantics kept from the reference:
 
 reg_hip_batch_new_keyframes (default false): detect() hands the candidates of ALL new keyframes of an update (loop_detector.hpp:57-68) to the
 device in one grouped call and replays the reference's order on the host (LoopDetector._detect_grouped).
+reg_hip_batch_pairs (default false; acts only together with reg_hip_batch_new_keyframes): where the engine refuses the grouped call (NDT_OMP,
+FAST_VGICP) the groups are flattened into (new keyframe, candidate) pairs and matched in ONE hgs_align_pairs, the best candidate selected per
+group on the host.
 """
 from __future__ import annotations
 
@@ -85,7 +88,8 @@ class LoopDetector:
         self.last_edge_accum_distance = 0.0
         self.shard = shard  # optional hdl_graph_slam_amd.distributed.CandidateShard (multi-GPU)
         self.batch_new_keyframes = bool(get("reg_hip_batch_new_keyframes", False))
-        self.last_detect_grouped = False   # whether the last detect() went through the grouped call
+        self.batch_pairs = bool(get("reg_hip_batch_pairs", False))
+        self.last_detect_grouped = False   # whether the last detect() went through the grouped (or paired) call
 
     def detect(self, keyframes: Sequence[KeyFrame], new_keyframes: Sequence[KeyFrame]) -> List[Loop]:
         self.last_detect_grouped = False
@@ -110,7 +114,8 @@ class LoopDetector:
           3. the host replays the loop in order: gate against the running value (a keyframe that now fails is skipped, its records are
              discarded — the sequential loop would not have matched it), selection and threshold (:147-168), raise the value on acceptance.
         A record depends on its own target, source and guess only (bitwise), so what the replay reads is what matching() would have read.
-        Returns None when the engine does not serve the grouped call (NDT_OMP, FAST_VGICP): the caller runs the sequential loop."""
+        Returns None when the engine does not serve the grouped call (NDT_OMP, FAST_VGICP) and reg_hip_batch_pairs is off: the caller runs the
+        sequential loop.  With the key on, the same groups go through one align_pairs — records bitwise per problem, as the grouped call's."""
         entry = self.last_edge_accum_distance
         groups = []
         for nk in new_keyframes:
@@ -126,8 +131,17 @@ class LoopDetector:
         records, best, rc = reg.loop_match_groups([self._resident(nk) for nk, _ in groups], [[self._resident(c) for c in cands] for _, cands in groups],
                                                   guesses, self.fitness_score_max_range, return_status=True)
         if rc == L.HGS_ERR_UNSUPPORTED:
-            return None
-        reg._check(rc)
+            if not self.batch_pairs:
+                return None
+            records = reg.align_pairs([self._resident(nk) for nk, cands in groups for _ in cands], [self._resident(c) for _, cands in groups for c in cands],
+                                      [g for gs in guesses for g in gs], self.fitness_score_max_range)
+            best, first = [], 0
+            for _, cands in groups:                                                       # candidate_id and best are per group, as the grouped call's
+                records["candidate_id"][first:first + len(cands)] = np.arange(len(cands))
+                best.append(select_best(records[first:first + len(cands)]))
+                first += len(cands)
+        else:
+            reg._check(rc)
         loops, first = [], 0
         for g, (nk, cands) in enumerate(groups):
             rec = records[first:first + len(cands)]

@@ -59,38 +59,91 @@ class ScanMatchingOdometry:
 
     def matching(self, stamp: float, cloud, msf_delta=None) -> np.ndarray:
         """Returns odom = keyframe_pose * trans (Eigen::Matrix4f semantics: float32 products)."""
+        filtered, guess = self.before_align(stamp, cloud, msf_delta)
+        if guess is None:
+            self.registration.setInputTarget(self.keyframe)
+            return np.eye(4, dtype=np.float32)
+        self.registration.setInputSource(filtered)
+        result = self.registration.align(guess)                     # :210
+        self.last_result = result
+        odom, switched = self.after_align(stamp, filtered, bool(result.converged), result.matrix())
+        if switched:
+            self.registration.setInputTarget(self.keyframe)
+        return odom
+
+    # The two halves of matching() around the registration, without a word to the engine: LockstepOdometry runs them per stream around one align_pairs.
+    def before_align(self, stamp: float, cloud, msf_delta=None):
+        """(filtered cloud, guess); guess None: the first sweep, which has become the keyframe (the caller makes it the target)."""
         if self.keyframe is None:                                   # :166-174
             self.prev_trans = np.eye(4, dtype=np.float32)
             self.keyframe_pose = np.eye(4, dtype=np.float32)
             self.keyframe_stamp = stamp
             self.keyframe = self.downsample(cloud)
-            self.registration.setInputTarget(self.keyframe)
             self.num_keyframes = 1
-            return np.eye(4, dtype=np.float32)
+            return self.keyframe, None
         filtered = self.downsample(cloud)                           # :176-177
-        self.registration.setInputSource(filtered)
         guess = self.prev_trans if msf_delta is None else (self.prev_trans @ np.asarray(msf_delta, np.float32)).astype(np.float32)
-        result = self.registration.align(guess)                     # :210
-        self.last_result = result
-        if not result.converged:                                    # :214-218
-            return (self.keyframe_pose @ self.prev_trans).astype(np.float32)
-        trans = np.asarray(result.matrix(), np.float32)             # :220
+        return filtered, guess
+
+    def after_align(self, stamp: float, filtered, converged: bool, matrix):
+        """The decisions of :214-252 on a registration's outcome: (odom, whether `filtered` has become the keyframe — the caller makes it the target)."""
+        if not converged:                                           # :214-218
+            return (self.keyframe_pose @ self.prev_trans).astype(np.float32), False
+        trans = np.asarray(matrix, np.float32)                      # :220
         odom = (self.keyframe_pose @ trans).astype(np.float32)
         if self.transform_thresholding:                             # :223-233
             delta = (np.linalg.inv(self.prev_trans) @ trans).astype(np.float32)
             dx = float(np.linalg.norm(delta[:3, 3]))
             da = _rotation_angle(delta[:3, :3])
             if dx > self.max_acceptable_trans or da > self.max_acceptable_angle:
-                return (self.keyframe_pose @ self.prev_trans).astype(np.float32)
+                return (self.keyframe_pose @ self.prev_trans).astype(np.float32), False
         self.prev_trans = trans                                     # :236
         delta_trans = float(np.linalg.norm(trans[:3, 3]))           # :241-243
         delta_angle = _rotation_angle(trans[:3, :3])
         delta_time = stamp - self.keyframe_stamp
         if delta_trans > self.keyframe_delta_trans or delta_angle > self.keyframe_delta_angle or delta_time > self.keyframe_delta_time:
             self.keyframe = filtered                                # :245-252
-            self.registration.setInputTarget(self.keyframe)
             self.keyframe_pose = odom
             self.keyframe_stamp = stamp
             self.prev_trans = np.eye(4, dtype=np.float32)
             self.num_keyframes += 1
-        return odom
+            return odom, True
+        return odom, False
+
+
+class LockstepOdometry:
+    """n odometry streams on ONE engine, one device batch per sweep time: the reference runs one ScanMatchingOdometryNodelet per LiDAR, each a
+    launch-bound chain per sweep; here the streams that have a keyframe register (keyframe i, filtered sweep i, guess i) in one align_pairs
+    (hgs_align_pairs: the engine's own target and source play no part) and then take the per-stream decisions of
+    scan_matching_odometry_nodelet.cpp:214-252 unchanged.  A keyframe switch replaces that stream's resident target.  The clouds are resident
+    DeviceClouds of `registration` (or host clouds, which are uploaded)."""
+
+    def __init__(self, registration, n_streams: int, **nodelet_params):
+        self.registration = registration
+        self.streams = [ScanMatchingOdometry(registration, **nodelet_params) for _ in range(n_streams)]
+        self.last_records = None
+
+    def _resident(self, cloud):
+        return cloud if hasattr(cloud, "_h") else self.registration.upload(cloud)
+
+    def matching(self, stamp: float, clouds, msf_deltas=None):
+        """One sweep per stream (None: the stream has none at this time) -> the list of their odom matrices (None where there was no sweep)."""
+        assert len(clouds) == len(self.streams)
+        odoms = [None] * len(self.streams)
+        work = []
+        for i, (st, cloud) in enumerate(zip(self.streams, clouds)):
+            if cloud is None:
+                continue
+            filtered, guess = st.before_align(stamp, cloud, None if msf_deltas is None else msf_deltas[i])
+            if guess is None:
+                st.keyframe = self._resident(st.keyframe)
+                odoms[i] = np.eye(4, dtype=np.float32)
+            else:
+                work.append((i, self._resident(filtered), guess))
+        if work:
+            rec = self.registration.align_pairs([self.streams[i].keyframe for i, _, _ in work], [f for _, f, _ in work], [g for _, _, g in work])
+            self.last_records = rec
+            for k, (i, filtered, _) in enumerate(work):
+                T = np.array(rec["final_transformation"][k], np.float32).reshape(4, 4).T
+                odoms[i], _ = self.streams[i].after_align(stamp, filtered, bool(rec["converged"][k]), T)
+        return odoms

@@ -241,6 +241,24 @@ class RegistrationHIP:
         self._check(rc)
         return out, best
 
+    def align_pairs(self, targets, sources, guesses, max_range=None, return_status: bool = False):
+        """n independent registrations in one device batch (hgs_align_pairs), every registration method: sources[i] against targets[i] from
+        guesses[i] — resident DeviceClouds, which may repeat in any role.  max_range: getFitnessScore(max_range) behind every registration
+        (None: fitness_score NaN, num_inliers 0, as align).  Returns the record array of loop_match_batch, candidate_id = i.  The engine's own
+        target and source stay as they are.  return_status: do not raise but return (records, status)."""
+        n = len(sources)
+        assert len(targets) == n and len(guesses) == n
+        tptr = (C.c_void_p * max(n, 1))(*[(t._h if t is not None else None) for t in targets])
+        sptr = (C.c_void_p * max(n, 1))(*[(s._h if s is not None else None) for s in sources])
+        g = np.ascontiguousarray(np.stack([L.colmajor16(T) for T in guesses]) if n else np.zeros((0, 16), np.float32))
+        out = np.zeros(n, dtype=L.RESULT_DTYPE)
+        rng = None if max_range is None else C.byref(C.c_double(float(max_range)))
+        rc = L.lib().hgs_align_pairs(self._h, tptr, sptr, g.ctypes.data_as(C.c_void_p), rng, n, out.ctypes.data_as(C.c_void_p))
+        if return_status:
+            return out, rc
+        self._check(rc)
+        return out
+
     # ---- sharded batch: one process per GPU, records all-gathered by RCCL on the engine's stream (include/hgs_registration.h)
     @staticmethod
     def comm_unique_id() -> bytes:

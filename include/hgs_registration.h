@@ -188,6 +188,23 @@ int hgs_loop_match_groups(hgs_handle* h, hgs_cloud* const* targets, size_t n_gro
                           const float* guesses /* 16 floats per candidate, column-major */,
                           double max_range, hgs_result* out /* one per candidate */,
                           int32_t* best /* n_groups entries, -1 = none; NULL ok */);
+/* n INDEPENDENT registrations in one batch, every registration method: problem i registers sources[i] against targets[i] from the guess at
+ * guesses + 16 * i with the handle's method and parameters.  The primitive under the grouped call (repeat a target, hgs_select_best per group —
+ * and the way to serve several new keyframes under HGS_NDT_OMP / HGS_FAST_VGICP, which hgs_loop_match_groups refuses) and under several odometry
+ * streams in one process (one pair per sensor and sweep, in lock-step).
+ * max_range non-NULL: getFitnessScore(*max_range) runs behind every registration, fitness_score and num_inliers are filled as hgs_loop_match_batch
+ * fills them; NULL: no fitness pass, fitness_score is NaN and num_inliers 0 as hgs_align returns them.  out[i].candidate_id = i.
+ * Every record is bitwise what a fresh engine with the same parameters returns for hgs_set_target_cloud(targets[i]) +
+ * hgs_loop_match_batch({sources[i]}, guess i, max_range): a problem's result depends on its own points only.
+ * The handle's own target and source (hgs_set_*) are neither read nor written.  A cloud may appear any number of times in either role — the same
+ * pair twice, targets[i] == sources[i]: every problem has its own scratch.
+ * n == 0 returns HGS_OK.  HGS_ERR_INVALID_ARGUMENT: a NULL array or entry, a cloud of another handle, n > INT_MAX; nothing has been touched.
+ * HGS_ERR_UNSUPPORTED: HGS_FAST_VGICP and the voxel grid of one target exceeds INT_MAX cells (see hgs_align) — the whole call, hgs_last_error names the
+ * first pair with that target and the grid; the engine stays usable.  An HGS_NDT_OMP target without a valid cell is no error (as hgs_loop_match_batch).
+ * An additive symbol: HGS_ABI_VERSION is unchanged. */
+int hgs_align_pairs(hgs_handle* h, hgs_cloud* const* targets /* n */, hgs_cloud* const* sources /* n */,
+                    const float* guesses /* 16 * n, column-major */, const double* max_range /* NULL: no fitness pass */, size_t n,
+                    hgs_result* out /* n */);
 /* Pure host helper: the sequential selection rule above applied to an arbitrary record list (used after the
  * multi-GPU all-gather of per-candidate records). */
 int hgs_select_best(const hgs_result* records, size_t n, int32_t* best);
