@@ -312,6 +312,95 @@ __device__ __forceinline__ float nn1_exclusive_bound(float d2_inclusive) {
   return __uint_as_float(u < 0x7f7fffffu ? u : 0x7f7fffffu);
 }
 
+// The wave-uniform bookkeeping of a quad walk (wave_nn1_quad and wave_walk_quad run the same one): which node comes next, where its
+// record is parked, which children are still owed a visit.  Everything here lives in SGPRs and is touched only on a descend or a pop;
+// a group step reads `rec` and nothing else.
+//   lvl   the level of `node`: (k - binary depth) / 2.  The children of a level-1 node are leaves; a level-l record is parked in
+//         slot min(l, kParkLevels), the leaf quad in slot 0.
+//   pend  bit 4 * l + c: child c of the group last evaluated at level l + 1 was wanted and has not been entered.  Deeper levels sit in
+//         lower nibbles, so the lowest set bit IS the lowest pending child of the deepest pending group: one find-first-one per pop.
+struct QuadCursor {
+  unsigned node;
+  int lvl;
+  unsigned long long pend;
+  float* park;
+  const float* rec;  // the parked group record of `node`
+  const Float4* nodes;
+  const Float4* leaves;  // leaf record of leaf NODE id n (not leaf index): leaves + 8 * n
+
+  __device__ __forceinline__ float* slot(int l) const { return park + 128 * (l < kParkLevels ? l : kParkLevels); }
+  // k >= 2.  An odd height starts at the virtual node 0 whose group holds {empty, empty, node 2, node 3}.
+  __device__ __forceinline__ void start(const BvhView& t, int k, float* park_) {
+    node = (k & 1) ? 0u : 1u, lvl = (k + 1) >> 1, pend = 0ull, park = park_;
+    nodes = t.nodes, leaves = t.lpts - 8 * (size_t)t.P;
+    float* s = slot(lvl);
+    fetch_quad(nodes, s);
+    rec = s + 32 * node;
+  }
+  __device__ __forceinline__ bool at_leaf_parent() const { return lvl == 1; }
+  __device__ __forceinline__ unsigned first_child() const { return node << 2; }
+  // all four leaves below `node` with one fetch (slot 0)
+  __device__ __forceinline__ void fetch_leaf_quad() const { fetch_quad(leaves + 8 * (size_t)first_child(), park); }
+  // enter child c of `node`; the other wanted children (any) stay pending.  The four child records arrive with one fetch.
+  __device__ __forceinline__ void descend(unsigned any, int c) {
+    lvl -= 1;
+    pend |= (unsigned long long)(any & ~(1u << c)) << (4 * lvl);
+    const unsigned base = first_child();
+    float* s = slot(lvl);
+    fetch_quad(nodes + 8 * (size_t)base, s);
+    node = base + (unsigned)c;
+    rec = s + 32 * c;
+  }
+  // backtrack: enter the lowest pending child of the deepest pending group (false: nothing is pending, the walk is over).  Its record
+  // is parked unless its level shares the top slot.
+  __device__ __forceinline__ bool pop() {
+    if (!pend) return false;
+    const int b = __builtin_ctzll(pend);
+    pend ^= 1ull << b;
+    const int l = b >> 2, c = b & 3;
+    const unsigned quad = (node >> (2 * (l - lvl))) & ~3u;
+    node = quad + (unsigned)c;
+    lvl = l;
+    float* s = slot(l);
+    if (l >= kParkLevels) fetch_quad(nodes + 8 * (size_t)quad, s);
+    rec = s + 32 * c;
+    return true;
+  }
+};
+
+// bit c: some lane of the wave wants child c.  Four ballots whose masks never leave the scalar unit: every bit is a scalar select on
+// "mask != 0".  Bit 0 written like the others (mask != 0 ? 1 : 0) is a zero-extended i1, which hipcc materialises in a VGPR and reads
+// back (s_cselect_b64, v_cndmask, v_readfirstlane — also when it is spelled with a population count or a shift, which are folded back
+// to it); selected together with bit 1 it stays an s_cselect_b32.
+__device__ __forceinline__ unsigned wave_any4(bool w0, bool w1, bool w2, bool w3) {
+  const unsigned long long m0 = __ballot(w0), m1 = __ballot(w1), m2 = __ballot(w2), m3 = __ballot(w3);
+  const unsigned lo = m0 != 0ull ? (m1 != 0ull ? 3u : 1u) : (m1 != 0ull ? 2u : 0u);
+  return lo | (m2 != 0ull ? 4u : 0u) | (m3 != 0ull ? 8u : 0u);
+}
+
+// The slot (0..3) of the nearest child this lane wants, -1 when it wants none: w[c] is the child's box distance, +inf where the lane
+// does not want it.  Selects only — written as nested conditionals it compiles to three levels of divergent branches.
+__device__ __forceinline__ int nearest_wanted(float w0, float w1, float w2, float w3) {
+  const float dmin = fminf(fminf(w0, w1), fminf(w2, w3));
+  int p = w2 == dmin ? 2 : 3;
+  p = w1 == dmin ? 1 : p;
+  p = w0 == dmin ? 0 : p;
+  return dmin == INFINITY ? -1 : p;
+}
+
+// The leaves `todo` of a parked leaf quad, visited in place starting with leaf c.  Every visit tightens the bounds, so the siblings
+// still owed a visit are re-tested after it (wanted() -> bit per child) and the ones nobody wants any more are dropped; after the
+// quad's last leaf there is nothing to re-test.
+template <class Wanted, class Visit>
+__device__ __forceinline__ void visit_leaf_quad(unsigned todo, int c, Wanted&& wanted, Visit&& visit) {
+  do {  // (one latch, one exit, an if without an else: with early returns the compiler's control-flow structurizer adds two flag blocks per leaf)
+    visit(c);
+    todo &= ~(1u << c);
+    if (todo) todo &= wanted();
+    c = todo ? __builtin_ctz(todo) : 0;
+  } while (todo);
+}
+
 // TRACK: also keep the best leaf and the number of leaves that reached the minimum (what nn1_resolve_leaf needs)
 template <bool ORDERED, bool TRACK>
 __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* kParkFloats, wave-private, 512-byte aligned */, const F3& q0, bool active,
@@ -329,8 +418,7 @@ __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* k
   int leaf = -1, cnt = 0;
   float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
   auto wanted = [&]() -> unsigned {
-    return (__ballot(d0 <= best) != 0ull ? 1u : 0u) | (__ballot(d1 <= best) != 0ull ? 2u : 0u) | (__ballot(d2 <= best) != 0ull ? 4u : 0u) |
-           (__ballot(d3 <= best) != 0ull ? 8u : 0u);
+    return wave_any4(d0 <= best, d1 <= best, d2 <= best, d3 <= best);
   };
   auto visit_leaf = [&](const float* rec, int ldnode) {
     const hgs_f16v xy = *reinterpret_cast<const hgs_f16v*>(rec);
@@ -357,14 +445,11 @@ __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* k
       visit_leaf(park, t.P + lf);
     }
   } else if (t.n > 0) {
-    unsigned node = (k & 1) ? 0u : 1u;
-    int bd = (k & 1) ? -1 : 0;
-    unsigned long long pend = 0;
-    const auto slot_of = [&](int depth) { const int s = (k - depth) >> 1; return park + 128 * (s < kParkLevels ? s : kParkLevels); };
-    fetch_quad(t.nodes, slot_of(bd));
+    QuadCursor cur;
+    cur.start(t, k, park);
     for (;;) {
       {  // the group of `node`: boxes of its four grandchildren  {mnx[4], mny[4], mnz[4], mxx[4]} {mxy[4], mxz[4]}
-        const float* rec = slot_of(bd) + 32 * (node & 3u);
+        const float* rec = cur.rec;
         const hgs_f16v lo = *reinterpret_cast<const hgs_f16v*>(rec);
         const hgs_f8v hi = *reinterpret_cast<const hgs_f8v*>(rec + 16);
         const hgs_f2 d01 = pk_box_dist2(qx, qy, qz, hgs_f2{lo[0], lo[1]}, hgs_f2{lo[4], lo[5]}, hgs_f2{lo[8], lo[9]}, hgs_f2{lo[12], lo[13]}, hgs_f2{hi[0], hi[1]},
@@ -377,42 +462,20 @@ __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* k
       if (any) {
         int cstar = __builtin_ctz(any);
         if (ORDERED) {  // the nearest child the middle lane of the packet wants (else the lowest wanted slot)
-          const float w0 = d0 <= best ? d0 : INFINITY, w1 = d1 <= best ? d1 : INFINITY, w2 = d2 <= best ? d2 : INFINITY, w3 = d3 <= best ? d3 : INFINITY;
-          const float dmin = fminf(fminf(w0, w1), fminf(w2, w3));
-          const int pref = dmin == INFINITY ? -1 : (w0 == dmin ? 0 : (w1 == dmin ? 1 : (w2 == dmin ? 2 : 3)));
+          const int pref = nearest_wanted(d0 <= best ? d0 : INFINITY, d1 <= best ? d1 : INFINITY, d2 <= best ? d2 : INFINITY, d3 <= best ? d3 : INFINITY);
           const int p = __builtin_amdgcn_readlane(pref, order_lane);
           if (p >= 0) cstar = p;
         }
-        const int cd = bd + 2;
-        const unsigned base = node << 2;
-        if (cd == k) {  // the children are leaves: all four records with one fetch, visited in place
-          fetch_quad(t.lpts + 8 * (size_t)(base - (unsigned)t.P), park);
-          unsigned todo = any;
-          int c = cstar;
-          while (todo) {
-            todo &= ~(1u << c);
-            visit_leaf(park + 32 * c, (int)(base + (unsigned)c));
-            todo &= wanted();  // the visit tightened the bounds: drop the leaves nobody wants any more
-            c = todo ? __builtin_ctz(todo) : 0;
-          }
-        } else {
-          pend |= (unsigned long long)(any & ~(1u << cstar)) << (4 * (cd >> 1));
-          fetch_quad(t.nodes + 8 * (size_t)base, slot_of(cd));
-          node = base + (unsigned)cstar;
-          bd = cd;
+        if (!cur.at_leaf_parent()) {
+          cur.descend(any, cstar);
           continue;
         }
+        // the children are leaves: all four records with one fetch, visited in place
+        cur.fetch_leaf_quad();
+        const unsigned base = cur.first_child();
+        visit_leaf_quad(any, cstar, wanted, [&](int c) { visit_leaf(park + 32 * c, (int)(base + (unsigned)c)); });
       }
-      if (!pend) break;
-      // backtrack: the lowest pending child of the deepest pending group; its record is parked unless its level shares the top slot
-      const int idx = (63 - __clzll((long long)pend)) >> 2;
-      const unsigned nib = (unsigned)(pend >> (4 * idx)) & 0xfu;
-      const int c = __builtin_ctz(nib);
-      pend &= ~(1ull << (4 * idx + c));
-      const int pcd = 2 * idx + (k & 1);
-      node = ((node >> (bd - pcd)) & ~3u) + (unsigned)c;
-      bd = pcd;
-      if (((k - bd) >> 1) >= kParkLevels) fetch_quad(t.nodes + 8 * (size_t)(node & ~3u), slot_of(bd));
+      if (!cur.pop()) break;
     }
   }
   best_out = best;
@@ -474,18 +537,14 @@ __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, con
   }
   float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
   auto wanted = [&]() -> unsigned {
-    return (__ballot(lane.wants(d0)) != 0ull ? 1u : 0u) | (__ballot(lane.wants(d1)) != 0ull ? 2u : 0u) | (__ballot(lane.wants(d2)) != 0ull ? 4u : 0u) |
-           (__ballot(lane.wants(d3)) != 0ull ? 8u : 0u);
+    return wave_any4(lane.wants(d0), lane.wants(d1), lane.wants(d2), lane.wants(d3));
   };
-  unsigned node = (k & 1) ? 0u : 1u;
-  int bd = (k & 1) ? -1 : 0;
-  unsigned long long pend = 0;
-  const auto slot_of = [&](int depth) { const int s = (k - depth) >> 1; return park + 128 * (s < kParkLevels ? s : kParkLevels); };
-  fetch_quad(t.nodes, slot_of(bd));
+  QuadCursor cur;
+  cur.start(t, k, park);
   for (;;) {
     HGS_PROBE_COUNT(0);
     {
-      const float* rec = slot_of(bd) + 32 * (node & 3u);
+      const float* rec = cur.rec;
       const hgs_f16v lo = *reinterpret_cast<const hgs_f16v*>(rec);
       const hgs_f8v hi = *reinterpret_cast<const hgs_f8v*>(rec + 16);
       const hgs_f2 d01 = pk_box_dist2(qx, qy, qz, hgs_f2{lo[0], lo[1]}, hgs_f2{lo[4], lo[5]}, hgs_f2{lo[8], lo[9]}, hgs_f2{lo[12], lo[13]}, hgs_f2{hi[0], hi[1]},
@@ -498,45 +557,26 @@ __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, con
     if (any) {
       int cstar = __builtin_ctz(any);
       {  // the nearest child the middle lane of the packet wants (else the lowest wanted slot)
-        const float w0 = lane.wants(d0) ? d0 : INFINITY, w1 = lane.wants(d1) ? d1 : INFINITY, w2 = lane.wants(d2) ? d2 : INFINITY, w3 = lane.wants(d3) ? d3 : INFINITY;
-        const float dmin = fminf(fminf(w0, w1), fminf(w2, w3));
-        const int pref = dmin == INFINITY ? -1 : (w0 == dmin ? 0 : (w1 == dmin ? 1 : (w2 == dmin ? 2 : 3)));
+        const int pref = nearest_wanted(lane.wants(d0) ? d0 : INFINITY, lane.wants(d1) ? d1 : INFINITY, lane.wants(d2) ? d2 : INFINITY, lane.wants(d3) ? d3 : INFINITY);
         const int p = __builtin_amdgcn_readlane(pref, order_lane);
         if (p >= 0) cstar = p;
       }
-      const int cd = bd + 2;
-      const unsigned base = node << 2;
-      if (cd == k) {
-        unsigned todo = any;
-        for (unsigned c = 0; c < 4; c++)
-          if (base + c - skip_lo < skip_n) todo &= ~(1u << c);  // leaves the caller has handled
-        if (todo) {
-          fetch_quad(t.lpts + 8 * (size_t)(base - (unsigned)t.P), park);
-          int c = (todo >> cstar) & 1u ? cstar : __builtin_ctz(todo);
-          while (todo) {
-            todo &= ~(1u << c);
-            visit(park + 32 * c, base + (unsigned)c);
-            todo &= wanted();
-            c = todo ? __builtin_ctz(todo) : 0;
-          }
-        }
-      } else {
-        pend |= (unsigned long long)(any & ~(1u << cstar)) << (4 * (cd >> 1));
-        fetch_quad(t.nodes + 8 * (size_t)base, slot_of(cd));
-        node = base + (unsigned)cstar;
-        bd = cd;
+      if (!cur.at_leaf_parent()) {
+        cur.descend(any, cstar);
         continue;
       }
+      const unsigned base = cur.first_child();
+      unsigned todo = any;
+      if (skip_n != 0u) {
+        for (unsigned c = 0; c < 4; c++)
+          if (base + c - skip_lo < skip_n) todo &= ~(1u << c);  // leaves the caller has handled
+      }
+      if (todo) {
+        cur.fetch_leaf_quad();
+        visit_leaf_quad(todo, (todo >> cstar) & 1u ? cstar : __builtin_ctz(todo), wanted, [&](int c) { visit(park + 32 * c, base + (unsigned)c); });
+      }
     }
-    if (!pend) return;
-    const int idx = (63 - __clzll((long long)pend)) >> 2;
-    const unsigned nib = (unsigned)(pend >> (4 * idx)) & 0xfu;
-    const int c = __builtin_ctz(nib);
-    pend &= ~(1ull << (4 * idx + c));
-    const int pcd = 2 * idx + (k & 1);
-    node = ((node >> (bd - pcd)) & ~3u) + (unsigned)c;
-    bd = pcd;
-    if (((k - bd) >> 1) >= kParkLevels) fetch_quad(t.nodes + 8 * (size_t)(node & ~3u), slot_of(bd));
+    if (!cur.pop()) return;
   }
 }
 
