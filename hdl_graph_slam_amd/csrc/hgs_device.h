@@ -258,6 +258,34 @@ void launch_pf_mean_knn_dist(hipStream_t s, CloudDesc d, int mean_k, double* dis
 void launch_pf_statistical(hipStream_t s, CloudDesc d, const double* dist, double* stats, double stddev_mul, unsigned* keep);
 void launch_pf_to_cloud(hipStream_t s, const float4* in, int n, float4* raw, float* intensity, CloudMeta* meta_to_reset, const CloudDesc* desc = nullptr, CloudDesc* desc_out = nullptr);
 
+// the prefilter of several sweeps in one batch (hgs_prefilter_batch): the sweeps lie concatenated in the work buffers, sweep s in [off, off + n) of every
+// array, its current points at the front of that slice.  One record per sweep in a device table; the kernels run one grid row (blockIdx.y) per sweep.
+struct PfSweep {
+  int off, n;         // host: the sweep's slice
+  int count;          // k_pfb_load: n; every compacting stage: the points it kept
+  int deskew, frame;  // host: whether w / rows apply
+  float w[3];         // host: the gyro rate, negated (pf_deskew_point)
+  double scan_period;
+  float rows[12];     // host: PfFrame::rows
+  unsigned meta[16];  // the voxel-grid record of k_pf_bbox / k_pf_grid, initialised by k_pfb_load
+};
+constexpr int kPfBatchOrdinalBits = 12;  // sort key of the batched voxel grid: sweep ordinal << 32 | voxel key
+void launch_pfb_load(hipStream_t s, const float4* staged, PfSweep* sweeps, int nsweeps, int max_n, float4* out);
+void launch_pfb_distance_flags(hipStream_t s, const float4* pts, const PfSweep* sweeps, int nsweeps, int max_n, double near_thresh, double far_thresh, unsigned* keep);
+void launch_pfb_compact(hipStream_t s, const float4* in, PfSweep* sweeps, int nsweeps, int max_n, const unsigned* keep, const unsigned* slot, float4* out);
+void launch_pfb_bbox(hipStream_t s, const float4* pts, PfSweep* sweeps, int nsweeps, int max_n, int dist_filter, double near_thresh, double far_thresh);
+void launch_pfb_grid(hipStream_t s, PfSweep* sweeps, int nsweeps, float inv_leaf);
+void launch_pfb_voxel_keys(hipStream_t s, const float4* pts, const PfSweep* sweeps, int nsweeps, int max_n, float inv_leaf, unsigned long long* keys, unsigned* vals,
+                           int dist_filter, double near_thresh, double far_thresh);
+void launch_pfb_voxel_heads(hipStream_t s, const unsigned long long* keys, const PfSweep* sweeps, int nsweeps, int max_n, unsigned* head);
+void launch_pfb_voxel_centroids(hipStream_t s, const float4* pts, const unsigned long long* keys, const unsigned* vals, const unsigned* head, const unsigned* slot,
+                                PfSweep* sweeps, int nsweeps, int max_n, float4* out, unsigned* ukeys /* may be null */);
+void launch_pfb_grid_radius_flags(hipStream_t s, const float4* cen, const unsigned* ukeys, const PfSweep* sweeps, int nsweeps, int max_n, float inv_leaf, float radius,
+                                  float r2, int min_neighbors, unsigned* keep);
+// descs: the new clouds' resident descriptors (also what launch_bbox_count reads behind this), each written to *desc_outs[s]
+void launch_pfb_to_cloud(hipStream_t s, const float4* in, const PfSweep* sweeps, const CloudDesc* descs, CloudDesc* const* desc_outs, float* const* intensities, int nsweeps,
+                         int max_m);
+
 // floor detection (apps/floor_detection_nodelet.cpp:110-238; hgs_floor.h)
 void launch_floor_clip_flags(hipStream_t s, const float4* raw, const float* intensity, int n, FloorConsts c, float4* out /* {x, y, z, intensity} */, unsigned* keep);
 void launch_knn_cov_raw(hipStream_t s, const CloudDesc* descs /* one cloud */, int max_n, int k, int qpw, int gather, double* raw_stage /* max_n * 6 doubles, sorted order */);

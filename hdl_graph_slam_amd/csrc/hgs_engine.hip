@@ -164,6 +164,8 @@ struct hgs_handle {
   int ndt_chunk = 0;             // largest queue grab in items (0: the default, 8; 1 = one tile per grab); HGS_NDT_CHUNK (A/B runs)
   int ndt_sort = -1;       // NDT source order: -1 Hilbert order if the source has an index, 1 build the index first, 0 input order (HGS_NDT_SORT, A/B runs)
   DeviceBuffer pf_a, pf_b, pf_keep, pf_slot, pf_small, pf_dist;  // prefilter work space
+  DeviceBuffer pf_table;         // hgs_prefilter_batch: the sweep table (PfSweep per sweep)
+  PinnedBuffer h_pf_table;       // ... and where its counts and overflow flags are read back to
   PinnedBuffer h_results, h_small, h_flags, h_comm;  // h_flags: host-mapped progress mirror (Progress)
   PinnedRing up;                   // small uploads (descriptors, guesses, plans)
   PinnedRing up_points;            // small point uploads: pinned chunks the host packs into (upload_points_packed)
@@ -268,23 +270,38 @@ constexpr size_t kUploadChunkPoints = 16384;     // 256 KB per pinned chunk
 #define HGS_UPLOAD_PARALLEL_POINTS 49152  // (A/B knob: a huge value keeps every upload on the calling thread)
 #endif
 constexpr size_t kUploadParallelPoints = HGS_UPLOAD_PARALLEL_POINTS;  // from three chunks on the pack pool helps (below: one thread, the ring of pinned chunks)
-int upload_points_packed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const float4** dev) {
-  HGS_HIP(h, h->staging.reserve(std::max<size_t>(n, 1) * sizeof(float4)));
-  *dev = h->staging.as<float4>();
+// The pinned image of the large uploads: opened (the previous upload's DMA has left it, room for `records`) in front of the packing, closed (event behind
+// the last DMA) after it.  A single upload opens and closes it around its own records; hgs_prefilter_batch opens it once for the concatenated image of all
+// its sweeps, so that a sweep's packing does not wait for the DMA of the sweep in front.
+int upload_image_open(hgs_handle* h, size_t records) {
+  if (h->up_big_pending) {
+    HGS_HIP(h, hipEventSynchronize(h->up_big_event));  // the previous upload's DMA has left the pinned image (it finished long ago)
+    h->up_big_pending = false;
+  }
+  HGS_HIP(h, h->up_big.reserve(records * sizeof(float4)));
+  return HGS_OK;
+}
+int upload_image_close(hgs_handle* h) {
+  if (!h->up_big_event) HGS_HIP(h, hipEventCreateWithFlags(&h->up_big_event, hipEventDisableTiming));
+  HGS_HIP(h, hipEventRecord(h->up_big_event, h->stream));
+  h->up_big_pending = true;
+  return HGS_OK;
+}
+// n records to h->staging[off ..) (reserved by the caller).  in_image: the caller has opened the pinned image for a concatenated upload that holds these
+// records at `off` and closes it behind the last one.
+int upload_points_at(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, size_t off, bool in_image) {
   const bool has_intensity = stride_bytes >= 20;
   const char* src = static_cast<const char*>(pts);
+  float4* const dev = h->staging.as<float4>() + off;
   if (n >= kUploadParallelPoints) {
     // large cloud: kWorkers + this thread pack chunks into ONE pinned image; this thread sends chunk c down as soon as it is ready (in order)
-    if (h->up_big_pending) {
-      HGS_HIP(h, hipEventSynchronize(h->up_big_event));  // the previous upload's DMA has left the pinned image (it finished long ago)
-      h->up_big_pending = false;
-    }
-    HGS_HIP(h, h->up_big.reserve(n * sizeof(float4)));
+    if (!in_image) HGS_TRY(upload_image_open(h, n));
+    float4* const image = h->up_big.as<float4>() + (in_image ? off : 0);
     const size_t nchunks = (n + kUploadChunkPoints - 1) / kUploadChunkPoints;
     std::vector<std::atomic<unsigned char>> ready(nchunks);
     for (auto& r : ready) r.store(0, std::memory_order_relaxed);
     PackPool::Job job;
-    job.src = src, job.dst = h->up_big.as<float>(), job.n = n, job.stride = stride_bytes, job.chunk = kUploadChunkPoints, job.nchunks = nchunks;
+    job.src = src, job.dst = reinterpret_cast<float*>(image), job.n = n, job.stride = stride_bytes, job.chunk = kUploadChunkPoints, job.nchunks = nchunks;
     job.has_intensity = has_intensity, job.ready = ready.data();
     h->pack_pool.post(&job);
     hipError_t err = hipSuccess;
@@ -292,13 +309,11 @@ int upload_points_packed(hgs_handle* h, const void* pts, size_t n, size_t stride
       while (!ready[c].load(std::memory_order_acquire))
         if (!PackPool::help(job)) std::this_thread::yield();
       const size_t i0 = c * kUploadChunkPoints, m = std::min(kUploadChunkPoints, n - i0);
-      if (err == hipSuccess) err = hipMemcpyAsync(h->staging.as<float4>() + i0, h->up_big.as<float4>() + i0, m * sizeof(float4), hipMemcpyHostToDevice, h->stream);
+      if (err == hipSuccess) err = hipMemcpyAsync(dev + i0, image + i0, m * sizeof(float4), hipMemcpyHostToDevice, h->stream);
     }
     h->pack_pool.retire();  // (`job` and `ready` live on this stack frame)
     HGS_HIP(h, err);
-    if (!h->up_big_event) HGS_HIP(h, hipEventCreateWithFlags(&h->up_big_event, hipEventDisableTiming));
-    HGS_HIP(h, hipEventRecord(h->up_big_event, h->stream));
-    h->up_big_pending = true;
+    if (!in_image) HGS_TRY(upload_image_close(h));
     return HGS_OK;
   }
   for (size_t i0 = 0; i0 < n; i0 += kUploadChunkPoints) {
@@ -319,10 +334,15 @@ int upload_points_packed(hgs_handle* h, const void* pts, size_t n, size_t stride
         dst[4 * i] = f[0], dst[4 * i + 1] = f[1], dst[4 * i + 2] = f[2], dst[4 * i + 3] = 0.f;
       }
     }
-    HGS_HIP(h, hipMemcpyAsync(h->staging.as<float4>() + i0, staged, m * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+    HGS_HIP(h, hipMemcpyAsync(dev + i0, staged, m * sizeof(float4), hipMemcpyHostToDevice, h->stream));
     HGS_HIP(h, h->up_points.commit(slot, h->stream));
   }
   return HGS_OK;
+}
+int upload_points_packed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const float4** dev) {
+  HGS_HIP(h, h->staging.reserve(std::max<size_t>(n, 1) * sizeof(float4)));
+  *dev = h->staging.as<float4>();
+  return upload_points_at(h, pts, n, stride_bytes, 0, false);
 }
 
 // ---- cloud allocation --------------------------------------------------------------------------------------
@@ -2326,29 +2346,29 @@ extern "C" int hgs_prefilter_params_default(hgs_prefilter_params* p) try {
   return status_of_current_exception(nullptr);
 }
 
-// the one sequence behind hgs_prefilter, hgs_prefilter_deskewed and hgs_prefilter_framed.  imu_angular_velocity null: no deskewing; sensor_to_base null:
-// no transform (then the launches and their arguments are those of the two older entry points)
-static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
-                          double scan_period, const float* sensor_to_base, hgs_cloud** out) {
-  ApiLock lock(h);
-  if (!h || !p || !out || (n > 0 && !pts) || stride_bytes < 12 || (stride_bytes % 4) != 0 || n > (size_t)1 << 30) return HGS_ERR_INVALID_ARGUMENT;
-  if (p->downsample_method < HGS_DOWNSAMPLE_NONE || p->downsample_method > HGS_DOWNSAMPLE_APPROX_VOXELGRID || p->outlier_removal_method < HGS_OUTLIER_NONE ||
-      p->outlier_removal_method > HGS_OUTLIER_RADIUS || (p->downsample_method != HGS_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)) ||
-      (p->outlier_removal_method == HGS_OUTLIER_STATISTICAL && (p->statistical_mean_k < 1 || p->statistical_mean_k > 62)) ||
-      (p->outlier_removal_method == HGS_OUTLIER_RADIUS && (!(p->radius_radius > 0) || p->radius_min_neighbors < 0)))
-    return HGS_ERR_INVALID_ARGUMENT;
-  // ang_v(x, y, z) as floats, times -1 (:219-220); an empty imu_queue passes the cloud as it is (:184-186)
+static bool prefilter_params_ok(const hgs_prefilter_params* p) {
+  return !(p->downsample_method < HGS_DOWNSAMPLE_NONE || p->downsample_method > HGS_DOWNSAMPLE_APPROX_VOXELGRID || p->outlier_removal_method < HGS_OUTLIER_NONE ||
+           p->outlier_removal_method > HGS_OUTLIER_RADIUS || (p->downsample_method != HGS_DOWNSAMPLE_NONE && !(p->downsample_resolution > 0)) ||
+           (p->outlier_removal_method == HGS_OUTLIER_STATISTICAL && (p->statistical_mean_k < 1 || p->statistical_mean_k > 62)) ||
+           (p->outlier_removal_method == HGS_OUTLIER_RADIUS && (!(p->radius_radius > 0) || p->radius_min_neighbors < 0)));
+}
+// what one sweep brings besides its points, checked and in the kernels' form: w = -ang_v as floats (null gyro sample: no deskewing, scan period 0),
+// the upper three rows of sensor_to_base row-major (null: no transform)
+struct PfSweepArgs {
   float w[3] = {0.f, 0.f, 0.f};
-  const float* deskew_w = nullptr;
+  bool deskew = false, framed = false;
+  double scan_period = 0.0;
+  PfFrame frame{};
+};
+static int prefilter_sweep_args(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const double* imu_angular_velocity, double scan_period,
+                                const float* sensor_to_base, PfSweepArgs* a) {
+  if ((n > 0 && !pts) || stride_bytes < 12 || (stride_bytes % 4) != 0 || n > (size_t)1 << 30) return HGS_ERR_INVALID_ARGUMENT;
+  // ang_v(x, y, z) as floats, times -1 (:219-220); an empty imu_queue passes the cloud as it is (:184-186)
   if (imu_angular_velocity) {
     if (!std::isfinite(scan_period)) return HGS_ERR_INVALID_ARGUMENT;
-    for (int a = 0; a < 3; a++) w[a] = -(float)imu_angular_velocity[a];
-    deskew_w = w;
-  } else {
-    scan_period = 0.0;
+    for (int k = 0; k < 3; k++) a->w[k] = -(float)imu_angular_velocity[k];
+    a->deskew = true, a->scan_period = scan_period;
   }
-  PfFrame frame_rows;
-  const PfFrame* frame = nullptr;
   if (sensor_to_base) {  // column-major 4x4: a rigid transform's bottom row; the rotation block is not looked at (pcl::transformPointCloud does not either)
     bool finite = true;
     for (int k = 0; k < 16; k++) finite = finite && std::isfinite(sensor_to_base[k]);
@@ -2357,9 +2377,23 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
       return HGS_ERR_INVALID_ARGUMENT;
     }
     for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 4; c++) frame_rows.rows[4 * r + c] = sensor_to_base[4 * c + r];
-    frame = &frame_rows;
+      for (int c = 0; c < 4; c++) a->frame.rows[4 * r + c] = sensor_to_base[4 * c + r];
+    a->framed = true;
   }
+  return HGS_OK;
+}
+
+// the one sequence behind hgs_prefilter, hgs_prefilter_deskewed and hgs_prefilter_framed.  imu_angular_velocity null: no deskewing; sensor_to_base null:
+// no transform (then the launches and their arguments are those of the two older entry points)
+static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
+                          double scan_period, const float* sensor_to_base, hgs_cloud** out) {
+  ApiLock lock(h);
+  if (!h || !p || !out || !prefilter_params_ok(p)) return HGS_ERR_INVALID_ARGUMENT;
+  PfSweepArgs args;
+  HGS_TRY(prefilter_sweep_args(h, pts, n, stride_bytes, imu_angular_velocity, scan_period, sensor_to_base, &args));
+  const float* deskew_w = args.deskew ? args.w : nullptr;
+  scan_period = args.scan_period;
+  const PfFrame* frame = args.framed ? &args.frame : nullptr;
   HGS_TRY(set_device(h));
   *out = nullptr;
   StageTimer tm(h, HGS_STAGE_PREFILTER);
@@ -2508,6 +2542,198 @@ extern "C" int hgs_prefilter_deskewed(hgs_handle* h, const void* pts, size_t n, 
 extern "C" int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
                                     double scan_period, const float* sensor_to_base, hgs_cloud** out) try {
   return prefilter_impl(h, pts, n, stride_bytes, p, imu_angular_velocity, scan_period, sensor_to_base, out);
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+// ---- several sweeps in one batch (include/hgs_registration.h; the k_pfb_* kernels of hgs_kernels.hip) -------------------------------------------------
+namespace {
+
+// Which parameter sets the batch runs itself: no downsampling or pcl::VoxelGrid, behind it no outlier removal or RadiusOutlierRemoval on the voxel grid
+// (what prefilter_impl calls grid_radius).  Everything else — ApproximateVoxelGrid's sequential history table, the outlier removals that need a search
+// tree per cloud — runs sweep after sweep through prefilter_impl inside the call.
+bool prefilter_batched(const hgs_handle* h, const hgs_prefilter_params* p) {
+  if (p->downsample_method == HGS_DOWNSAMPLE_APPROX_VOXELGRID) return false;
+  if (p->outlier_removal_method == HGS_OUTLIER_NONE) return true;
+  return p->downsample_method == HGS_DOWNSAMPLE_VOXELGRID && h->prefilter_fast && p->outlier_removal_method == HGS_OUTLIER_RADIUS &&
+         p->radius_radius / p->downsample_resolution <= 4.0;
+}
+
+void free_clouds(hgs_cloud** out, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    if (out[i]) cloud_free(out[i]);
+    out[i] = nullptr;
+  }
+}
+
+// the sweeps one after the other: prefilter_impl's sequence per sweep (S = 1, and the parameter sets the batch does not run)
+int prefilter_each(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_t S, const hgs_prefilter_params* p, hgs_cloud** out) {
+  for (size_t i = 0; i < S; i++) {
+    const hgs_prefilter_sweep& w = sweeps[i];
+    const int rc = prefilter_impl(h, w.pts, w.n, w.stride_bytes, p, w.imu_angular_velocity, w.scan_period, w.sensor_to_base, &out[i]);
+    if (rc != HGS_OK) {
+      h->err = "sweep " + std::to_string(i) + ": " + h->err;
+      free_clouds(out, S);
+      return rc;
+    }
+  }
+  return HGS_OK;
+}
+
+int prefilter_batch_impl(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_t S, const std::vector<PfSweepArgs>& args, const hgs_prefilter_params* p,
+                         hgs_cloud** out) {
+  std::vector<size_t> off(S + 1, 0);
+  size_t max_n = 0;
+  for (size_t i = 0; i < S; i++) off[i + 1] = off[i] + sweeps[i].n, max_n = std::max(max_n, sweeps[i].n);
+  const size_t total = off[S], cap = std::max<size_t>(total, 1);
+  const size_t table_bytes = S * sizeof(PfSweep);
+  HGS_HIP(h, h->pf_a.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_b.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_keep.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_slot.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_table.reserve(table_bytes));
+  HGS_HIP(h, h->h_pf_table.reserve(table_bytes));
+  HGS_HIP(h, h->staging.reserve(cap * sizeof(float4)));
+  PfSweep* d_sweeps = h->pf_table.as<PfSweep>();
+  const int nS = (int)S, mx = (int)max_n;
+  {
+    StageTimer tm(h, HGS_STAGE_UPLOAD);
+    void* staged = nullptr;
+    int slot = 0;
+    HGS_HIP(h, h->up.stage(table_bytes, &staged, &slot));
+    PfSweep* t = static_cast<PfSweep*>(staged);
+    bool any_large = false;
+    for (size_t i = 0; i < S; i++) {
+      t[i] = PfSweep{};
+      t[i].off = (int)off[i], t[i].n = (int)sweeps[i].n;
+      t[i].deskew = args[i].deskew, t[i].frame = args[i].framed, t[i].scan_period = args[i].scan_period;
+      std::memcpy(t[i].w, args[i].w, sizeof(t[i].w));
+      std::memcpy(t[i].rows, args[i].frame.rows, sizeof(t[i].rows));
+      any_large = any_large || sweeps[i].n >= kUploadParallelPoints;
+    }
+    HGS_HIP(h, hipMemcpyAsync(d_sweeps, t, table_bytes, hipMemcpyHostToDevice, h->stream));
+    HGS_HIP(h, h->up.commit(slot, h->stream));
+    // ONE staging image, every sweep at its offset; the large sweeps share one opening of the pinned image (its event logic: upload_image_open / _close)
+    if (any_large) HGS_TRY(upload_image_open(h, total));
+    for (size_t i = 0; i < S; i++)
+      if (sweeps[i].n > 0) HGS_TRY(upload_points_at(h, sweeps[i].pts, sweeps[i].n, sweeps[i].stride_bytes, off[i], any_large));
+    if (any_large) HGS_TRY(upload_image_close(h));
+  }
+  StageTimer tm(h, HGS_STAGE_PREFILTER);
+  float4* cur = h->pf_a.as<float4>();
+  float4* other = h->pf_b.as<float4>();
+  unsigned* keep = h->pf_keep.as<unsigned>();
+  unsigned* slot = h->pf_slot.as<unsigned>();
+  launch_pfb_load(h->stream, h->staging.as<float4>(), d_sweeps, nS, mx, cur);
+  const bool voxelgrid = total > 0 && p->downsample_method == HGS_DOWNSAMPLE_VOXELGRID;
+  const int inline_dist = (voxelgrid && p->use_distance_filter && h->prefilter_fast) ? 1 : 0;
+  if (total > 0 && p->use_distance_filter && !inline_dist) {
+    launch_pfb_distance_flags(h->stream, cur, d_sweeps, nS, mx, p->distance_near_thresh, p->distance_far_thresh, keep);
+    HGS_TRY(scan_u32(h, keep, slot, total));
+    launch_pfb_compact(h->stream, cur, d_sweeps, nS, mx, keep, slot, other);
+    std::swap(cur, other);
+  }
+  if (voxelgrid) {
+    const float inv_leaf = 1.0f / (float)p->downsample_resolution;
+    launch_pfb_bbox(h->stream, cur, d_sweeps, nS, mx, inline_dist, p->distance_near_thresh, p->distance_far_thresh);
+    launch_pfb_grid(h->stream, d_sweeps, nS, inv_leaf);
+    HGS_TRY(reserve_sort_pairs(h, total));
+    launch_pfb_voxel_keys(h->stream, cur, d_sweeps, nS, mx, inv_leaf, h->sort_keys[0].as<unsigned long long>(), h->sort_vals[0].as<unsigned>(), inline_dist,
+                          p->distance_near_thresh, p->distance_far_thresh);
+    int ordinal_bits = 0;
+    while (((size_t)1 << ordinal_bits) < S) ordinal_bits++;
+    HGS_TRY(sort_pairs(h, total, 0, 32 + ordinal_bits));  // stable: every sweep keeps its slice, in the order its own sort over bits 0..31 gives
+    launch_pfb_voxel_heads(h->stream, h->sort_keys[1].as<unsigned long long>(), d_sweeps, nS, mx, keep);
+    HGS_TRY(scan_u32(h, keep, slot, total));
+    const bool grid_radius = p->outlier_removal_method == HGS_OUTLIER_RADIUS;  // (prefilter_batched: on the voxel grid, or not here at all)
+    unsigned* ukeys = nullptr;
+    if (grid_radius) {
+      HGS_HIP(h, h->pf_ukeys.reserve(total * sizeof(uint32_t)));
+      ukeys = h->pf_ukeys.as<unsigned>();
+    }
+    launch_pfb_voxel_centroids(h->stream, cur, h->sort_keys[1].as<unsigned long long>(), h->sort_vals[1].as<unsigned>(), keep, slot, d_sweeps, nS, mx, other, ukeys);
+    std::swap(cur, other);
+    if (grid_radius) {
+      launch_pfb_grid_radius_flags(h->stream, cur, ukeys, d_sweeps, nS, mx, inv_leaf, (float)p->radius_radius, (float)(p->radius_radius * p->radius_radius),
+                                   p->radius_min_neighbors, keep);
+      HGS_TRY(scan_u32(h, keep, slot, total));
+      launch_pfb_compact(h->stream, cur, d_sweeps, nS, mx, keep, slot, other);
+      std::swap(cur, other);
+    }
+  }
+  HGS_HIP(h, hipGetLastError());
+  // every sweep's count and voxel-grid overflow flag in ONE copy (the table)
+  const PfSweep* hs = h->h_pf_table.as<PfSweep>();
+  HGS_HIP(h, hipMemcpyAsync(h->h_pf_table.p, d_sweeps, table_bytes, hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  if (voxelgrid)
+    for (size_t i = 0; i < S; i++)
+      if (sweeps[i].n > 0 && hs[i].meta[12]) {
+        h->err = "sweep " + std::to_string(i) + ": prefilter: voxel grid too fine for this cloud (index overflow; pcl::VoxelGrid refuses it too)";
+        return HGS_ERR_INVALID_ARGUMENT;
+      }
+  size_t max_m = 0;
+  for (size_t i = 0; i < S; i++) {
+    const size_t m = (size_t)std::max(0, hs[i].count);
+    HGS_TRY(cloud_alloc(h, m, &out[i]));
+    max_m = std::max(max_m, m);
+  }
+  // the new clouds' descriptors, where each goes, and the intensity arrays: one staged block
+  const size_t o_out = align_up(S * sizeof(CloudDesc), 16), o_int = o_out + S * sizeof(CloudDesc*), tail_bytes = o_int + S * sizeof(float*);
+  HGS_HIP(h, h->descs.reserve(tail_bytes));
+  void* staged = nullptr;
+  int ring_slot = 0;
+  HGS_HIP(h, h->up.stage(tail_bytes, &staged, &ring_slot));
+  char* hb = static_cast<char*>(staged);
+  for (size_t i = 0; i < S; i++) {
+    reinterpret_cast<CloudDesc*>(hb)[i] = resident_desc(out[i]);
+    reinterpret_cast<CloudDesc**>(hb + o_out)[i] = out[i]->dev_desc;
+    reinterpret_cast<float**>(hb + o_int)[i] = out[i]->intensity;
+  }
+  HGS_HIP(h, hipMemcpyAsync(h->descs.p, hb, tail_bytes, hipMemcpyHostToDevice, h->stream));
+  HGS_HIP(h, h->up.commit(ring_slot, h->stream));
+  char* db = h->descs.as<char>();
+  launch_pfb_to_cloud(h->stream, cur, d_sweeps, reinterpret_cast<const CloudDesc*>(db), reinterpret_cast<CloudDesc* const*>(db + o_out),
+                      reinterpret_cast<float* const*>(db + o_int), nS, (int)max_m);
+  launch_bbox_count(h->stream, reinterpret_cast<const CloudDesc*>(db), nS, (int)max_m);
+  HGS_HIP(h, hipGetLastError());
+  return HGS_OK;
+}
+
+}  // namespace
+
+extern "C" int hgs_prefilter_batch(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_t n_sweeps, const hgs_prefilter_params* p, hgs_cloud** out) try {
+  ApiLock lock(h);
+  if (!h || !p || !prefilter_params_ok(p)) return HGS_ERR_INVALID_ARGUMENT;
+  if (n_sweeps == 0) return HGS_OK;
+  if (!sweeps || !out) return HGS_ERR_INVALID_ARGUMENT;
+  if (n_sweeps > HGS_PREFILTER_BATCH_MAX_SWEEPS) {
+    h->err = "hgs_prefilter_batch: more than " + std::to_string(HGS_PREFILTER_BATCH_MAX_SWEEPS) + " sweeps in one call";
+    return HGS_ERR_INVALID_ARGUMENT;
+  }
+  static_assert(HGS_PREFILTER_BATCH_MAX_SWEEPS == 1 << kPfBatchOrdinalBits, "the sort key's ordinal bits");
+  std::vector<PfSweepArgs> args(n_sweeps);
+  size_t total = 0;
+  h->err.clear();
+  for (size_t i = 0; i < n_sweeps; i++) {
+    const hgs_prefilter_sweep& w = sweeps[i];
+    const int rc = prefilter_sweep_args(h, w.pts, w.n, w.stride_bytes, w.imu_angular_velocity, w.scan_period, w.sensor_to_base, &args[i]);
+    if (rc != HGS_OK) {
+      h->err = "sweep " + std::to_string(i) + ": " + (h->err.empty() ? std::string("invalid points, stride or scan period") : h->err);
+      return rc;
+    }
+    total += w.n;
+  }
+  if (total > (size_t)1 << 30) {
+    h->err = "hgs_prefilter_batch: more than 2^30 points in one call";
+    return HGS_ERR_INVALID_ARGUMENT;
+  }
+  HGS_TRY(set_device(h));
+  for (size_t i = 0; i < n_sweeps; i++) out[i] = nullptr;
+  if (n_sweeps == 1 || !prefilter_batched(h, p)) return prefilter_each(h, sweeps, n_sweeps, p, out);
+  const int rc = prefilter_batch_impl(h, sweeps, n_sweeps, args, p, out);
+  if (rc != HGS_OK) free_clouds(out, n_sweeps);
+  return rc;
 } catch (...) {
   return status_of_current_exception(h);
 }

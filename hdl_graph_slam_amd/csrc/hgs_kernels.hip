@@ -3041,6 +3041,281 @@ void launch_pf_to_cloud(hipStream_t s, const float4* in, int n, float4* raw, flo
                      desc ? desc_out : nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------ prefilter, several sweeps in one batch
+// hgs_prefilter_batch: the k_pf_* sequence above over S sweeps that lie concatenated in the work buffers (PfSweep, hgs_device.h).  Every kernel runs one grid
+// row per sweep (blockIdx.y, as k_bbox_count and k_hilbert_keys do for the clouds of an index build): a block never holds points of two sweeps, and a thread's
+// index within its row is the point's index within its OWN sweep — what the deskewing, the voxel grid's record and the neighbour search of a centroid depend
+// on.  Per point the arithmetic is that of the single kernels (the same device functions, the same expressions), so sweep s comes out bit for bit as
+// hgs_prefilter_framed gives it.  What is shared between the sweeps: ONE stable sort (key = sweep ordinal << 32 | voxel key: a sweep's entries keep their
+// slice and their single-sort order) and ONE exclusive scan per compaction (a sweep's output slot = scan value - the scan value at its slice's start).
+// Rows of sweeps shorter than the longest one end at once; the launch count does not depend on S.
+__global__ __launch_bounds__(kBlock) void k_pfb_load(const float4* __restrict__ staged, PfSweep* __restrict__ sweeps, float4* __restrict__ out) {
+  PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x, n = sw.n;
+  if (l == 0) {
+    sw.count = n;
+#pragma unroll
+    for (int k = 0; k < 16; k++) sw.meta[k] = k < 3 ? 0xffffffffu : 0u;
+  }
+  if (l >= n) return;
+  const float4 p = staged[sw.off + l];
+  float x = p.x, y = p.y, z = p.z;
+  if (sw.deskew) pf_deskew_point(sw.w[0], sw.w[1], sw.w[2], sw.scan_period, l, n, &x, &y, &z);
+  if (sw.frame) pf_transform_point(sw.rows, &x, &y, &z);
+  out[sw.off + l] = make_float4(x, y, z, p.w);
+}
+void launch_pfb_load(hipStream_t s, const float4* staged, PfSweep* sweeps, int nsweeps, int max_n, float4* out) {
+  hipLaunchKernelGGL(k_pfb_load, dim3(std::max(1, (max_n + kBlock - 1) / kBlock), nsweeps), dim3(kBlock), 0, s, staged, sweeps, out);
+}
+
+// the flag kernels write every entry of a sweep's slice (0 behind its current count): the scan runs over whole slices
+__global__ __launch_bounds__(kBlock) void k_pfb_distance_flags(const float4* __restrict__ pts, const PfSweep* __restrict__ sweeps, double near_thresh, double far_thresh,
+                                                               unsigned* __restrict__ keep) {
+  const PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= sw.n) return;
+  const int i = sw.off + l;
+  keep[i] = (l < sw.count && pf_distance_keeps(pts[i], near_thresh, far_thresh)) ? 1u : 0u;
+}
+void launch_pfb_distance_flags(hipStream_t s, const float4* pts, const PfSweep* sweeps, int nsweeps, int max_n, double near_thresh, double far_thresh, unsigned* keep) {
+  if (max_n > 0) hipLaunchKernelGGL(k_pfb_distance_flags, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, pts, sweeps, near_thresh, far_thresh, keep);
+}
+
+// k_pf_compact per sweep: the kept points move to the front of the sweep's slice of `out`, its count is taken at the slice's end
+__global__ __launch_bounds__(kBlock) void k_pfb_compact(const float4* __restrict__ in, PfSweep* __restrict__ sweeps, const unsigned* __restrict__ keep,
+                                                        const unsigned* __restrict__ slot, float4* __restrict__ out) {
+  PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x, n = sw.n, off = sw.off;
+  if (l >= n) return;
+  const int i = off + l;
+  const unsigned base = slot[off];
+  if (keep[i]) out[off + (int)(slot[i] - base)] = in[i];
+  if (l == n - 1) sw.count = (int)(slot[i] + keep[i] - base);
+}
+void launch_pfb_compact(hipStream_t s, const float4* in, PfSweep* sweeps, int nsweeps, int max_n, const unsigned* keep, const unsigned* slot, float4* out) {
+  if (max_n > 0) hipLaunchKernelGGL(k_pfb_compact, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, in, sweeps, keep, slot, out);
+}
+
+// k_pf_bbox per sweep: one set of atomics per block, into the block's own sweep's record
+__global__ __launch_bounds__(kBlock) void k_pfb_bbox(const float4* __restrict__ pts_all, PfSweep* __restrict__ sweeps, int dist_filter, double near_thresh, double far_thresh) {
+  PfSweep& sw = sweeps[blockIdx.y];
+  const int n = sw.count;
+  const float4* __restrict__ pts = pts_all + sw.off;
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int i0 = blockIdx.x * kBlock * kBboxPerThread + threadIdx.x; i0 < n; i0 += gridDim.x * kBlock * kBboxPerThread) {
+    float4 p[kBboxPerThread];
+#pragma unroll
+    for (int k = 0; k < kBboxPerThread; k++) {
+      const int i = i0 + k * kBlock;
+      p[k] = i < n ? pts[i] : make_float4(NAN, NAN, NAN, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < kBboxPerThread; k++)
+      if (finite3(p[k]) && (!dist_filter || pf_distance_keeps(p[k], near_thresh, far_thresh))) {
+        mn[0] = fminf(mn[0], p[k].x), mn[1] = fminf(mn[1], p[k].y), mn[2] = fminf(mn[2], p[k].z);
+        mx[0] = fmaxf(mx[0], p[k].x), mx[1] = fmaxf(mx[1], p[k].y), mx[2] = fmaxf(mx[2], p[k].z);
+      }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      mn[k] = fminf(mn[k], __shfl_down(mn[k], off, 64));
+      mx[k] = fmaxf(mx[k], __shfl_down(mx[k], off, 64));
+    }
+  __shared__ float s_mn[kBlock / 64][3], s_mx[kBlock / 64][3];
+  const int wave = (int)(threadIdx.x >> 6);
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 3; k++) s_mn[wave][k] = mn[k], s_mx[wave][k] = mx[k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; w++)
+      for (int k = 0; k < 3; k++) mn[k] = fminf(mn[k], s_mn[w][k]), mx[k] = fmaxf(mx[k], s_mx[w][k]);
+    if (mn[0] <= mx[0])
+      for (int k = 0; k < 3; k++) {
+        atomicMin(&sw.meta[k], f2ord(mn[k]));
+        atomicMax(&sw.meta[3 + k], f2ord(mx[k]));
+      }
+  }
+}
+void launch_pfb_bbox(hipStream_t s, const float4* pts, PfSweep* sweeps, int nsweeps, int max_n, int dist_filter, double near_thresh, double far_thresh) {
+  const int gx = std::max(1, (max_n + kBlock * kBboxPerThread - 1) / (kBlock * kBboxPerThread));
+  hipLaunchKernelGGL(k_pfb_bbox, dim3(gx, nsweeps), dim3(kBlock), 0, s, pts, sweeps, dist_filter, near_thresh, far_thresh);
+}
+// k_pf_grid, one thread per sweep
+__global__ __launch_bounds__(64) void k_pfb_grid(PfSweep* __restrict__ sweeps, int nsweeps, float inv_leaf) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= nsweeps) return;
+  unsigned* meta = sweeps[s].meta;
+  int* im = reinterpret_cast<int*>(meta);
+  if (meta[0] == 0xffffffffu) {  // no finite point
+    for (int k = 6; k < 13; k++) im[k] = 0;
+    return;
+  }
+  long long div[3];
+  for (int k = 0; k < 3; k++) {
+    im[6 + k] = (int)floorf(ord2f(meta[k]) * inv_leaf);
+    div[k] = (long long)(int)floorf(ord2f(meta[3 + k]) * inv_leaf) - im[6 + k] + 1;
+  }
+  const long long kMaxCells = 2147483647LL;
+  bool over = div[0] > kMaxCells;
+  if (!over) over = div[1] > kMaxCells / div[0];
+  if (!over) over = div[2] > kMaxCells / (div[0] * div[1]);
+  im[12] = over ? 1 : 0;
+  im[9] = 1, im[10] = over ? 0 : (int)div[0], im[11] = over ? 0 : (int)(div[0] * div[1]);
+}
+void launch_pfb_grid(hipStream_t s, PfSweep* sweeps, int nsweeps, float inv_leaf) {
+  hipLaunchKernelGGL(k_pfb_grid, dim3((nsweeps + 63) / 64), dim3(64), 0, s, sweeps, nsweeps, inv_leaf);
+}
+// k_pf_voxel_keys with the sweep's ordinal above the voxel key; vals: the point's position in the concatenated array
+__global__ __launch_bounds__(kBlock) void k_pfb_voxel_keys(const float4* __restrict__ pts, const PfSweep* __restrict__ sweeps, float inv_leaf,
+                                                           unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, int dist_filter, double near_thresh,
+                                                           double far_thresh) {
+  const PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= sw.n) return;
+  const int i = sw.off + l;
+  const int* im = reinterpret_cast<const int*>(sw.meta);
+  unsigned long long key = 0xffffffffull;
+  if (l < sw.count && !im[12]) {
+    const float4 p = pts[i];
+    if (finite3(p) && (!dist_filter || pf_distance_keeps(p, near_thresh, far_thresh))) {
+      const int ix = (int)floorf(p.x * inv_leaf) - im[6], iy = (int)floorf(p.y * inv_leaf) - im[7], iz = (int)floorf(p.z * inv_leaf) - im[8];
+      key = (unsigned long long)(unsigned)(ix * im[9] + iy * im[10] + iz * im[11]);
+    }
+  }
+  keys[i] = ((unsigned long long)blockIdx.y << 32) | key;
+  vals[i] = (unsigned)i;
+}
+void launch_pfb_voxel_keys(hipStream_t s, const float4* pts, const PfSweep* sweeps, int nsweeps, int max_n, float inv_leaf, unsigned long long* keys, unsigned* vals,
+                           int dist_filter, double near_thresh, double far_thresh) {
+  if (max_n > 0)
+    hipLaunchKernelGGL(k_pfb_voxel_keys, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, pts, sweeps, inv_leaf, keys, vals, dist_filter, near_thresh,
+                       far_thresh);
+}
+// (a key of the sweep in front differs in its upper half: no run crosses a slice's start)
+__global__ __launch_bounds__(kBlock) void k_pfb_voxel_heads(const unsigned long long* __restrict__ keys, const PfSweep* __restrict__ sweeps, unsigned* __restrict__ head) {
+  const PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= sw.n) return;
+  const int i = sw.off + l;
+  const unsigned long long k = keys[i];
+  head[i] = ((unsigned)k != 0xffffffffu && (l == 0 || keys[i - 1] != k)) ? 1u : 0u;
+}
+void launch_pfb_voxel_heads(hipStream_t s, const unsigned long long* keys, const PfSweep* sweeps, int nsweeps, int max_n, unsigned* head) {
+  if (max_n > 0) hipLaunchKernelGGL(k_pfb_voxel_heads, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, keys, sweeps, head);
+}
+__global__ __launch_bounds__(kBlock) void k_pfb_voxel_centroids(const float4* __restrict__ pts, const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                                const unsigned* __restrict__ head, const unsigned* __restrict__ slot, PfSweep* __restrict__ sweeps,
+                                                                float4* __restrict__ out, unsigned* __restrict__ ukeys /* may be null */) {
+  HGS_FP_STRICT
+  PfSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x, n = sw.n, off = sw.off;
+  if (l >= n) return;
+  const int i = off + l, end = off + n;
+  const unsigned base = slot[off];
+  if (l == n - 1) sw.count = (int)(slot[i] + head[i] - base);
+  if (!head[i]) return;
+  const unsigned long long key = keys[i];
+  const int o = off + (int)(slot[i] - base);
+  if (ukeys) ukeys[o] = (unsigned)key;
+  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
+  int cnt = 0;
+  for (int j = i; j < end && keys[j] == key; j++) {
+    const float4 p = pts[vals[j]];
+    sx += p.x, sy += p.y, sz += p.z, si += p.w;
+    cnt++;
+  }
+  const float fn = (float)cnt;
+  out[o] = make_float4(sx / fn, sy / fn, sz / fn, si / fn);
+}
+void launch_pfb_voxel_centroids(hipStream_t s, const float4* pts, const unsigned long long* keys, const unsigned* vals, const unsigned* head, const unsigned* slot,
+                                PfSweep* sweeps, int nsweeps, int max_n, float4* out, unsigned* ukeys) {
+  if (max_n > 0)
+    hipLaunchKernelGGL(k_pfb_voxel_centroids, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, pts, keys, vals, head, slot, sweeps, out, ukeys);
+}
+
+// k_pf_grid_radius_flags per sweep: a centroid's searches run over its own sweep's slice of the key table, with that sweep's grid record
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_pfb_grid_radius_flags(const float4* __restrict__ cen_all, const unsigned* __restrict__ ukeys_all, const PfSweep* __restrict__ sweeps,
+                                                                  float inv_leaf, float radius, float r2, int min_neighbors, unsigned* __restrict__ keep) {
+  static_assert(G == 4 || G == 8 || G == 16, "a power of two that divides the wave");
+  const PfSweep& sw = sweeps[blockIdx.y];
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  const int j = t / G, g = t & (G - 1);
+  const int m = sw.count, cap = sw.n;
+  const float4* __restrict__ cen = cen_all + sw.off;
+  const unsigned* __restrict__ ukeys = ukeys_all + sw.off;
+  int cnt = 0;
+  if (j < m) {
+    const int* im = reinterpret_cast<const int*>(sw.meta);
+    const float4 p = cen[j];
+    const F3 q = {p.x, p.y, p.z};
+    const int nx = im[10], ny = im[10] > 0 ? im[11] / im[10] : 0;
+    int lo[3], hi[3];
+    const float c[3] = {p.x, p.y, p.z};
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      lo[a] = (int)floorf((c[a] - radius) * inv_leaf - 1.0e-3f) - im[6 + a];
+      hi[a] = (int)floorf((c[a] + radius) * inv_leaf + 1.0e-3f) - im[6 + a];
+    }
+    lo[0] = max(lo[0], 0), lo[1] = max(lo[1], 0), lo[2] = max(lo[2], 0);
+    hi[0] = min(hi[0], nx - 1), hi[1] = min(hi[1], ny - 1);
+    int a = 0;
+    const int iz0 = lo[2] + g, iz1 = g == G - 1 ? hi[2] : min(iz0, hi[2]);
+    for (int iz = iz0; iz <= iz1 && cnt <= min_neighbors; iz++)
+      for (int iy = lo[1]; iy <= hi[1] && cnt <= min_neighbors; iy++) {
+        const long long row = (long long)iy * im[10] + (long long)iz * im[11];
+        const long long k0 = row + lo[0], k1 = row + hi[0];
+        if (k1 < 0 || k0 > 0xfffffffell) continue;
+        const unsigned key0 = (unsigned)max(k0, 0ll), key1 = (unsigned)min(k1, 0xfffffffell);
+        int b = a, step = a == 0 ? m : 1;
+        while (b < m && ukeys[b] < key0) a = b + 1, b = min(b + step, m), step <<= 1;
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (ukeys[mid] < key0) a = mid + 1;
+          else b = mid;
+        }
+        for (; a < m && ukeys[a] <= key1 && cnt <= min_neighbors; a++) {
+          const float4 o = cen[a];
+          cnt += dist2f(q, o.x, o.y, o.z) < r2 ? 1 : 0;
+        }
+      }
+  }
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if (g == 0 && j < cap) keep[sw.off + j] = (j < m && cnt > min_neighbors) ? 1u : 0u;
+}
+void launch_pfb_grid_radius_flags(hipStream_t s, const float4* cen, const unsigned* ukeys, const PfSweep* sweeps, int nsweeps, int max_n, float inv_leaf, float radius,
+                                  float r2, int min_neighbors, unsigned* keep) {
+  if (max_n <= 0) return;
+  const int layers = (int)ceilf(2.f * radius * inv_leaf + 2.0e-3f) + 2;  // (as launch_pf_grid_radius_flags)
+  const int G = layers <= 4 ? 4 : layers <= 8 ? 8 : 16;
+  const dim3 grid((unsigned)(((long long)max_n * G + kBlock - 1) / kBlock), nsweeps);
+  if (G == 4) hipLaunchKernelGGL(k_pfb_grid_radius_flags<4>, grid, dim3(kBlock), 0, s, cen, ukeys, sweeps, inv_leaf, radius, r2, min_neighbors, keep);
+  else if (G == 8) hipLaunchKernelGGL(k_pfb_grid_radius_flags<8>, grid, dim3(kBlock), 0, s, cen, ukeys, sweeps, inv_leaf, radius, r2, min_neighbors, keep);
+  else hipLaunchKernelGGL(k_pfb_grid_radius_flags<16>, grid, dim3(kBlock), 0, s, cen, ukeys, sweeps, inv_leaf, radius, r2, min_neighbors, keep);
+}
+
+// k_pf_to_cloud for every sweep's new cloud (descs[s].n_input = the sweep's final count, read back by the host in front of the allocation)
+__global__ __launch_bounds__(kBlock) void k_pfb_to_cloud(const float4* __restrict__ in, const PfSweep* __restrict__ sweeps, const CloudDesc* __restrict__ descs,
+                                                         CloudDesc* const* __restrict__ desc_outs, float* const* __restrict__ intensities) {
+  const CloudDesc d = descs[blockIdx.y];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) {
+    meta_reset(d.meta);
+    *desc_outs[blockIdx.y] = d;
+  }
+  if (i >= d.n_input) return;
+  const float4 p = in[sweeps[blockIdx.y].off + i];
+  const_cast<float4*>(d.raw)[i] = make_float4(p.x, p.y, p.z, __int_as_float(i));
+  intensities[blockIdx.y][i] = p.w;
+}
+void launch_pfb_to_cloud(hipStream_t s, const float4* in, const PfSweep* sweeps, const CloudDesc* descs, CloudDesc* const* desc_outs, float* const* intensities, int nsweeps,
+                         int max_m) {
+  hipLaunchKernelGGL(k_pfb_to_cloud, dim3(std::max(1, (max_m + kBlock - 1) / kBlock), nsweeps), dim3(kBlock), 0, s, in, sweeps, descs, desc_outs, intensities);
+}
+
 // ------------------------------------------------------------------------------------------------ floor detection
 // FloorDetectionNodelet::detect (apps/floor_detection_nodelet.cpp:110-180; hgs_floor.h).  The clip and the normal filter are flag kernels in front of
 // the prefilter's scan + k_pf_compact; the normals come from k_knn_cov's staged fp64 neighbourhood covariances.  RANSAC is a dense counting problem:

@@ -116,12 +116,19 @@ class LockstepOdometry:
     launch-bound chain per sweep; here the streams that have a keyframe register (keyframe i, filtered sweep i, guess i) in one align_pairs
     (hgs_align_pairs: the engine's own target and source play no part) and then take the per-stream decisions of
     scan_matching_odometry_nodelet.cpp:214-252 unchanged.  A keyframe switch replaces that stream's resident target.  The clouds are resident
-    DeviceClouds of `registration` (or host clouds, which are uploaded)."""
+    DeviceClouds of `registration` (or host clouds, which are uploaded).
 
-    def __init__(self, registration, n_streams: int, **nodelet_params):
+    prefilter_params (an hgs_prefilter_params): `matching` takes the RAW host sweeps and prefilters those of one sweep time in one prefilter_batch
+    (hgs_prefilter_batch; base_link_transforms: one sensor -> base_link matrix, or None, per stream) instead of one prefilter call per stream; the
+    streams' own `downsample` then stays the identity.  Without it nothing changes."""
+
+    def __init__(self, registration, n_streams: int, prefilter_params=None, base_link_transforms=None, **nodelet_params):
         self.registration = registration
         self.streams = [ScanMatchingOdometry(registration, **nodelet_params) for _ in range(n_streams)]
         self.last_records = None
+        self.prefilter_params = prefilter_params
+        self.base_link_transforms = [None] * n_streams if base_link_transforms is None else list(base_link_transforms)
+        assert len(self.base_link_transforms) == n_streams
 
     def _resident(self, cloud):
         return cloud if hasattr(cloud, "_h") else self.registration.upload(cloud)
@@ -129,6 +136,13 @@ class LockstepOdometry:
     def matching(self, stamp: float, clouds, msf_deltas=None):
         """One sweep per stream (None: the stream has none at this time) -> the list of their odom matrices (None where there was no sweep)."""
         assert len(clouds) == len(self.streams)
+        if self.prefilter_params is not None:
+            have = [i for i, c in enumerate(clouds) if c is not None]
+            filtered = self.registration.prefilter_batch([clouds[i] for i in have], self.prefilter_params,
+                                                         base_link_transforms=[self.base_link_transforms[i] for i in have])
+            clouds = list(clouds)
+            for i, f in zip(have, filtered):
+                clouds[i] = f
         odoms = [None] * len(self.streams)
         work = []
         for i, (st, cloud) in enumerate(zip(self.streams, clouds)):

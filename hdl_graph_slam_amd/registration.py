@@ -199,6 +199,32 @@ class RegistrationHIP:
                                                        float(scan_period), C.byref(h)))
         return DeviceCloud._adopt(self, h)
 
+    def prefilter_batch(self, clouds, params=None, imu_angular_velocities=None, scan_periods=0.1, base_link_transforms=None) -> list:
+        """`prefilter` of several sweeps in one device batch (hgs_prefilter_batch): the S LiDARs of one sweep time, or the next sweeps of a replayed run.
+        Returns one resident DeviceCloud per sweep, each bit for bit what prefilter(clouds[i], params, ...) returns.  One parameter set for all sweeps;
+        imu_angular_velocities / base_link_transforms: None, or one entry (or None) per sweep; scan_periods: one number, or one per sweep."""
+        if params is None:
+            params = L.HgsPrefilterParams()
+            self._check(L.lib().hgs_prefilter_params_default(C.byref(params)))
+        n = len(clouds)
+        per = lambda v: [None] * n if v is None else list(v)
+        ws, Ts = per(imu_angular_velocities), per(base_link_transforms)
+        periods = [float(scan_periods)] * n if np.isscalar(scan_periods) else [float(x) for x in scan_periods]
+        assert len(ws) == n and len(Ts) == n and len(periods) == n
+        sweeps = (L.HgsPrefilterSweep * max(n, 1))()
+        keep = []      # the arrays the pointers in `sweeps` refer to
+        for i, cloud in enumerate(clouds):
+            arr, m, stride = L.cloud_args(cloud)
+            w = None if ws[i] is None else np.ascontiguousarray(ws[i], np.float64).reshape(3)
+            T = None if Ts[i] is None else L.colmajor16(Ts[i])
+            keep += [arr, w, T]
+            sweeps[i].pts, sweeps[i].n, sweeps[i].stride_bytes, sweeps[i].scan_period = arr.ctypes.data, m, stride, periods[i]
+            sweeps[i].imu_angular_velocity = None if w is None else w.ctypes.data
+            sweeps[i].sensor_to_base = None if T is None else T.ctypes.data
+        out = (C.c_void_p * max(n, 1))()
+        self._check(L.lib().hgs_prefilter_batch(self._h, sweeps, n, C.byref(params), out))
+        return [DeviceCloud._adopt(self, C.c_void_p(out[i])) for i in range(n)]
+
     def map_cloud(self, keyframes, poses, resolution: float) -> DeviceCloud:
         """MapCloudGenerator::generate (src/hdl_graph_slam/map_cloud_generator.cpp:13-51) over resident keyframe clouds."""
         n = len(keyframes)

@@ -305,6 +305,29 @@ int hgs_prefilter_deskewed(hgs_handle* h, const void* pts, size_t n, size_t stri
 int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p,
                          const double* imu_angular_velocity /* NULL: no deskewing */, double scan_period,
                          const float sensor_to_base[16] /* column-major, NULL: no transform */, hgs_cloud** out);
+/* Several sweeps in one device batch: out[i] is, bit for bit, what hgs_prefilter_framed(sweep i, p) returns — the same count, points, order and
+ * intensities; a result depends on its own sweep's points only.  One parameter set for all sweeps (one nodelet configuration); the gyro sample, the scan
+ * period and the mount matrix are per sweep, each with hgs_prefilter_framed's meaning.  The S LiDARs of one sweep time, or the next sweeps of a recorded run
+ * that is replayed into a map, cost one launch sequence and one read-back instead of S: the sweeps lie concatenated on the device, the voxel grids share
+ * one sort (sweep ordinal in the key bits above the voxel index) and one scan per compaction.  Batched this way: downsample NONE or VOXELGRID with outlier
+ * removal NONE, or RADIUS on the voxel grid (radius_radius / downsample_resolution <= 4: every launch file that selects RADIUS).  Every other parameter
+ * set, and a call with one sweep, runs the single-sweep sequence per sweep inside the call, with the same results.
+ * n_sweeps == 0: HGS_OK.  A sweep with n == 0 yields an empty cloud.  HGS_ERR_INVALID_ARGUMENT, with nothing touched, for a NULL array, for a sweep that
+ * hgs_prefilter_framed would refuse (stride, n > 2^30, a non-finite scan period next to a gyro sample, a matrix with a non-finite entry or another bottom
+ * row than 0 0 0 1), for more than 2^30 points in total and for more than HGS_PREFILTER_BATCH_MAX_SWEEPS sweeps (the ordinal bits of the sort key).  A
+ * sweep whose voxel grid overflows ("too fine for this cloud") fails the WHOLE call with HGS_ERR_INVALID_ARGUMENT: hgs_last_error names the sweep, every
+ * out[i] is NULL and nothing is left allocated; the engine stays usable.  Touches neither the handle's target nor its source.
+ * An additive symbol and struct: HGS_ABI_VERSION is unchanged. */
+#define HGS_PREFILTER_BATCH_MAX_SWEEPS 4096
+typedef struct hgs_prefilter_sweep {
+  const void* pts;                    /* as hgs_prefilter */
+  size_t n;
+  size_t stride_bytes;
+  const double* imu_angular_velocity; /* [3], NULL: no deskewing of this sweep */
+  double scan_period;
+  const float* sensor_to_base;        /* column-major 4x4, NULL: no transform for this sweep */
+} hgs_prefilter_sweep;
+int hgs_prefilter_batch(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_t n_sweeps, const hgs_prefilter_params* p, hgs_cloud** out /* n_sweeps */);
 /* Copy a resident cloud back: out_pts[i] = {x, y, z, (1.0), intensity, ...} with the PointXYZI layout for stride >= 20,
  * packed xyz(+w) otherwise.  Needs room for hgs_cloud_size(c) records. */
 int hgs_cloud_download(hgs_cloud* c, void* out_pts, size_t stride_bytes);
