@@ -267,12 +267,29 @@ __device__ __forceinline__ const T* global_pointer(const T* p) {
   return p;
 #endif
 }
+template <typename T>
+__device__ __forceinline__ T* global_pointer_rw(T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
+#else
+  return p;
+#endif
+}
 __device__ __forceinline__ const TargetView& problem_target(const TargetView& t, int) { return t; }
 __device__ __forceinline__ TargetView problem_target(const TargetView* __restrict__ tviews, int b) {
   TargetView t = global_pointer(tviews)[b];
   t.nodes = global_pointer(t.nodes), t.pts = global_pointer(t.pts), t.lpts = global_pointer(t.lpts), t.cov = global_pointer(t.cov);
   t.meta = global_pointer(t.meta), t.seed_tab = global_pointer(t.seed_tab);
   return t;
+}
+// The same for cloud c of a launch over descriptors in HBM (k_knn_cov, k_cov_regularize): the record is read block-uniformly in front of the kernel's
+// first store — scalar loads — and its pointers are declared global, so the walk reads its records with global loads off scalar bases instead of flat
+// loads, which keep every base in a VGPR pair (one of them spilled in k_knn_cov) and wait on both memory counters.
+__device__ __forceinline__ CloudDesc problem_cloud(const CloudDesc* __restrict__ descs, int c) {
+  CloudDesc d = global_pointer(descs)[c];
+  d.raw = global_pointer(d.raw), d.pts = global_pointer_rw(d.pts), d.lpts = global_pointer_rw(d.lpts), d.nodes = global_pointer_rw(d.nodes);
+  d.cov = global_pointer_rw(d.cov), d.corr = global_pointer_rw(d.corr), d.meta = global_pointer_rw(d.meta);
+  return d;
 }
 
 // ------------------------------------------------------------------------------------------------ upload
@@ -404,6 +421,9 @@ __global__ __launch_bounds__(kBlock) void k_gather_sorted(const CloudDesc* descs
   const CloudDesc d = descs[blockIdx.y];
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= d.P * kLeaf) return;
+  // Pad points are +inf in EVERY coordinate and every point in front of nvalid is finite (the non-finite ones sort behind it): the k-NN insertion
+  // chain (KnnRadiusLane::insert, hgs_wave_bvh.h) takes squared distances unselected and relies on their never being NaN — a finite query against
+  // such a pad is +inf, never inf - inf.  A pad that is finite or NaN in some coordinate, or a query taken from behind nvalid, would break it.
   float4 p = make_float4(INFINITY, INFINITY, INFINITY, __int_as_float(-1));
   if (i < d.meta->nvalid) p = d.raw[sorted_vals[d.sort_off + i]];
   d.pts[i] = p;
@@ -522,13 +542,14 @@ template <int KMAX, int REG, int GATHER, bool WINDOW = false>
 __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const CloudDesc* descs, int k, int qpw, int reg_method, double* __restrict__ raw, int raw_stride) {
   constexpr bool REG_GENERAL = REG == 1;
   constexpr bool REPLAY = GATHER == 1, LISTS = GATHER == 2;
-  const CloudDesc d = descs[blockIdx.y];
-  const int n = d.meta->nvalid;
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
+  const int n = __builtin_amdgcn_readfirstlane(d.meta->nvalid);
   const int tile_pts = (kBlock / 64) * qpw;
   const int ntiles = (n + tile_pts - 1) / tile_pts;
   if (xcd_tile(blockIdx.x, ntiles) >= ntiles) return;
   const int lane = (int)(threadIdx.x & 63);
-  const int i = xcd_tile(blockIdx.x, ntiles) * tile_pts + (int)(threadIdx.x >> 6) * qpw + lane;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (a scalar: the wave's LDS areas and its first query are wave-uniform addresses)
+  const int i = xcd_tile(blockIdx.x, ntiles) * tile_pts + wave * qpw + lane;
   const bool active = lane < qpw && i < n;
   BvhView tv;
   tv.nodes = d.nodes, tv.pts = d.pts, tv.lpts = d.lpts, tv.P = d.P, tv.n = n;
@@ -538,9 +559,9 @@ __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const Clou
   __shared__ __attribute__((aligned(512))) float walk_slots[kBlock / 64][kParkFloats];
   __shared__ unsigned leaf_log[REPLAY ? kBlock / 64 : 1][REPLAY ? kKnnLeafLog : 1];
   __shared__ unsigned lane_lists[LISTS ? kKnnLaneList : 1][LISTS ? kBlock : 1];  // [entry][thread]: conflict-free for equal counts
-  float* slot = walk_slots[threadIdx.x >> 6];  // the quad walk's parking area; its first 128 bytes stage the replayed records
-  LeafLog log = {leaf_log[REPLAY ? threadIdx.x >> 6 : 0], REPLAY ? kKnnLeafLog : 0, 0};
-  const int i0 = i - lane;
+  float* slot = walk_slots[wave];  // the quad walk's parking area; its first 128 bytes stage the replayed records
+  LeafLog log = {leaf_log[REPLAY ? wave : 0], REPLAY ? kKnnLeafLog : 0, 0};
+  const int i0 = xcd_tile(blockIdx.x, ntiles) * tile_pts + wave * qpw;  // (wave-uniform, and known to be: the window, its trip count and the walk's skip window are scalars)
   // the pre-fill window [win0, win0 + win_n): whole leaves that contain the packet's own points; at least 32 points (>= k for every k hdl_graph_slam uses)
   // unless the cloud has fewer, at most 64 (39 when it is not the packet itself)
   // WINDOW = false (packets of 32 or 64 queries): the window is the packet itself, as in rounds 2-5 — the general form below costs the 64-candidate batch
@@ -564,7 +585,7 @@ __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const Clou
   {
     KnnRadiusLane<KMAX, GATHER != 0, LISTS> L;
     L.init(live, active);
-    L.list = &lane_lists[0][LISTS ? threadIdx.x : 0], L.stride = kBlock, L.cnt = 0, L.cap = kKnnLaneList;
+    L.list = &lane_lists[0][LISTS ? wave * 64 + lane : 0], L.stride = kBlock, L.cnt = 0, L.cap = kKnnLaneList;
     // The wave's window — its own 64 points (8 whole leaves of the Hilbert order) — holds every lane's first candidates: all-pairs
     // through v_readlane — the walk then starts with every list full and a bound within ~1.2x of
     // the final radius instead of +inf, which is what keeps it from wandering (3x fewer insertions and leaves).
@@ -572,11 +593,22 @@ __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const Clou
     // points around it.  A launch of less than one packet per SIMD lasts as long as its slowest wave, and those are the packets over sparse far returns at
     // ~4x the median's leaves (scripts/probes/knn_probe.py): shorter packets split them, but only behind a full window — with 16 own points the lists start
     // unfilled and the walk wanders, which is why round 6's first attempt at 16-query packets measured equal.)
-    for (int jj = 0; jj < win_n; jj++) {
-      const float px = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wp.x), jj)), py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wp.y), jj)),
-                  pz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wp.z), jj));
-      const float dd = dist2f(q, px, py, pz);
-      if (__ballot(dd < L.worst()) != 0ull) L.insert_wave(dd < L.worst() ? dd : FLT_MAX);
+    // Two window points per iteration, one packed distance (pk_dist2 == dist2f per half), inserted in index order: the list after every pair is what
+    // one point per iteration leaves.  An odd count ends with a single point.
+    {
+      auto window = [&](float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); };
+      const hgs_f2 qx = {q.x, q.x}, qy = {q.y, q.y}, qz = {q.z, q.z};
+      const int pairs_end = max(win_n, 0) & ~1;  // (a wave behind the cloud's end has a negative count)
+      for (int jj = 0; jj < pairs_end; jj += 2) {
+        const hgs_f2 dd = pk_dist2(qx, qy, qz, hgs_f2{window(wp.x, jj), window(wp.x, jj + 1)}, hgs_f2{window(wp.y, jj), window(wp.y, jj + 1)},
+                                   hgs_f2{window(wp.z, jj), window(wp.z, jj + 1)});
+        if (__ballot(dd.x < L.worst()) != 0ull) L.insert_wave(dd.x);
+        if (__ballot(dd.y < L.worst()) != 0ull) L.insert_wave(dd.y);
+      }
+      if (pairs_end < win_n) {
+        const float dd = dist2f(q, window(wp.x, pairs_end), window(wp.y, pairs_end), window(wp.z, pairs_end));
+        if (__ballot(dd < L.worst()) != 0ull) L.insert_wave(dd);
+      }
     }
     HGS_PROBE_TIME(1);
     if (walk)
@@ -633,7 +665,7 @@ __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const Clou
             leaf = leaf0 + (unsigned)__builtin_ctz(own_mask);
             own_mask &= own_mask - 1u;
           } else {
-            leaf = lane_lists[li++][threadIdx.x];
+            leaf = lane_lists[li++][wave * 64 + lane];
           }
           const hgs_f16v* rec = reinterpret_cast<const hgs_f16v*>(tv.lpts + 8 * (size_t)leaf);
           const hgs_f16v lo = rec[0], hi = rec[1];
@@ -698,7 +730,7 @@ __global__ __launch_bounds__(kBlock) HGS_KNN_OCCUPANCY void k_knn_cov(const Clou
 // The regularisation of the staged covariances (REG == 2): 48 bytes in, 24 out per point, one point per thread, nothing else live — the 3x3 Jacobi
 // eigen-decomposition that cost k_knn_cov<.., 1, ..> its 5-waves-per-SIMD register budget for the WHOLE search runs here at full occupancy.
 __global__ __launch_bounds__(kBlock) void k_cov_regularize(const CloudDesc* descs, const double* __restrict__ raw, int raw_stride, int reg_method) {
-  const CloudDesc d = descs[blockIdx.y];
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= d.meta->nvalid) return;
   const double* r = raw + ((size_t)blockIdx.y * (size_t)raw_stride + (size_t)i) * 6;
@@ -862,14 +894,6 @@ void launch_seed_grid_build(hipStream_t s, const float4* pts, const CloudMeta* m
 // kernel's first store — scalar loads — and its pointers are declared global like problem_target's (no flat loads or stores).  The fill is
 // k_seed_grid_build's: the atomicMin of sorted positions makes every entry the smallest position that hashes there, whatever the launch shape, so a table
 // is word for word what the single-cloud kernel writes.
-template <typename T>
-__device__ __forceinline__ T* global_pointer_rw(T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
-#else
-  return p;
-#endif
-}
 __device__ __forceinline__ SeedGridJob seed_grid_job(const SeedGridJob* __restrict__ jobs, int j) {
   SeedGridJob job = global_pointer(jobs)[j];
   job.pts = global_pointer(job.pts), job.meta = global_pointer(job.meta), job.tab = global_pointer_rw(job.tab);

@@ -503,15 +503,20 @@ __device__ __forceinline__ void nn1_resolve_leaf(const BvhView& t, const F3& q, 
   pos_out = pos, orig_out = pos >= 0 ? orig : -1;
 }
 
-// The quad walk for any Lane (concept of PacketWalk above): what k_knn_cov and the prefilter's outlier walks run.  Same
+// The quad walk for any Lane (concept of PacketWalk above): what k_knn_cov runs, in both passes (the prefilter's outlier walks run
+// wave_walk_multi).  All 64 lanes call it together from wave-uniform control flow — it reads its skip window from the first lane.  Same
 // traversal as wave_walk_multi<Lane, 1> — nearest-first by the order lane, leaves of a leaf-parent group in place with the
 // bounds re-tested after every visit, pending children entered directly, the skip window, the leaf log — with the records
 // fetched four at a time and parked per level (fetch_quad): one memory wait per group that has wanted children.
 template <class Lane>
-__device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, const F3& q, float* park /* kParkFloats */, int order_lane, unsigned skip_lo = 0,
-                                               unsigned skip_n = 0, LeafLog* log = nullptr) {
+__device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, const F3& q, float* park /* kParkFloats */, int order_lane, unsigned skip_lo_ = 0,
+                                               unsigned skip_n_ = 0, LeafLog* log = nullptr) {
   const int k = 31 - __clz(t.P);
   if (t.n <= 0) return;
+  // The skip window is the same for the whole wave, but callers derive it from the thread index: taken from the first lane it is a scalar,
+  // and with it the leaf-quad loop's `todo`, its leaf number and the parked record's address (as in wave_nn1_quad) — otherwise every
+  // leaf pays a v_ffbl, a v_cmp against the loop's exec mask and a per-lane LDS address.
+  const unsigned skip_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)skip_lo_), skip_n = (unsigned)__builtin_amdgcn_readfirstlane((int)skip_n_);
   const hgs_f2 qx = {q.x, q.x}, qy = {q.y, q.y}, qz = {q.z, q.z};
   auto visit = [&](const float* rec, unsigned ldnode) {
     if (log) {
@@ -602,14 +607,23 @@ struct KnnRadiusLane {
   // With <= the leaves this walk visits are a superset of the leaves the gather pass needs (box_d2 <= r2 <= worst at any time),
   // which is what lets k_knn_cov<.., REPLAY> replay the visited leaves instead of walking the tree a second time.
   __device__ __forceinline__ bool wants(float box_d2) const { return INCLUSIVE ? box_d2 <= worst() : box_d2 < worst(); }
-  __device__ __forceinline__ void insert(float x) {  // x < worst()
+  // Precondition: x is not NaN (any other value, also x >= worst(), which leaves the list as it is: see insert_wave).  A NaN would be taken for
+  // a small value by v_med3_f32 and corrupt the list; squared distances are never NaN because (1) stored points are finite (non-finite input
+  // points are dropped by the index build), (2) a pad point is +inf in EVERY coordinate (k_gather_sorted), so its distance is +inf and never
+  // inf - inf, and (3) no query is ever a pad point (queries are sorted positions < nvalid; idle lanes hold finite stand-ins and an all -1 list).
+  // Every stored value is >= -1, so the lowest slot's min(d[0], x) is the median of (-1, d[0], x): the chain is KMAX v_med3_f32 and nothing
+  // else (fminf costs two canonicalising v_max_f32 on top of its v_min_f32).
+  __device__ __forceinline__ void insert(float x) {
 #pragma unroll
     for (int i = KMAX - 1; i > 0; i--) d[i] = __builtin_amdgcn_fmed3f(d[i - 1], d[i], x);
-    d[0] = fminf(d[0], x);
+    d[0] = __builtin_amdgcn_fmed3f(-1.f, d[0], x);
   }
-  // The same from wave-uniform control flow (a lane with nothing to insert passes FLT_MAX, which leaves its list as it is): no
-  // divergent branch around the chain.  Stopping the chain early at the first five-slot segment no lane's value reaches (13 instead
-  // of 20 v_med3 on average) was measured and is slower (covariance stage 3.94 vs 3.56 ms: the ballots serialise the chain).
+  // The same from wave-uniform control flow, every lane with the distance it has: no divergent branch around the chain and no select in
+  // front of it.  A lane that does not accept x (x >= worst(), or an idle lane's all -1 list) keeps its list: the list is ascending, so
+  // for x >= d[KMAX-1] every med3(d[i-1], d[i], x) is d[i] and med3(-1, d[0], x) is d[0]; med3(-1, -1, x) is -1 for every x.  Distances
+  // are never NaN: queries and stored points are finite, pad points are +inf (distance +inf, never inf - inf).
+  // Stopping the chain early at the first five-slot segment no lane's value reaches (13 instead of 20 v_med3 on average) was measured
+  // and is slower (covariance stage 3.94 vs 3.56 ms: the ballots serialise the chain).
   __device__ __forceinline__ void insert_wave(float x) { insert(x); }
   __device__ __forceinline__ void visit_leaf(const hgs_f16v& xy, const hgs_f16v& zw, hgs_f2 qx, hgs_f2 qy, hgs_f2 qz, int base) {
     hgs_f2 dd[4];
@@ -624,8 +638,8 @@ struct KnnRadiusLane {
     }
 #pragma unroll
     for (int l = 0; l < 4; l++) {
-      if (__ballot(dd[l].x < worst()) != 0ull) { HGS_PROBE_COUNT(2); insert_wave(dd[l].x < worst() ? dd[l].x : FLT_MAX); }
-      if (__ballot(dd[l].y < worst()) != 0ull) { HGS_PROBE_COUNT(2); insert_wave(dd[l].y < worst() ? dd[l].y : FLT_MAX); }
+      if (__ballot(dd[l].x < worst()) != 0ull) { HGS_PROBE_COUNT(2); insert_wave(dd[l].x); }
+      if (__ballot(dd[l].y < worst()) != 0ull) { HGS_PROBE_COUNT(2); insert_wave(dd[l].y); }
     }
   }
 };
