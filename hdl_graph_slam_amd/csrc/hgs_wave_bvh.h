@@ -298,14 +298,32 @@ constexpr int kParkLevels = 4;                     // leaf quad + three group le
 constexpr int kParkSlots = kParkLevels + 1;        // + the slot all higher levels share
 constexpr int kParkFloats = kParkSlots * 128;      // wave-private LDS floats (2560 bytes)
 
-// the four records (512 contiguous bytes) starting at `quad` -> LDS slot
-__device__ __forceinline__ void fetch_quad(const Float4* quad, float* slot) {
+// FETCH ON ENTRY.  The child quad of a node is a function of the node alone, so its load is issued when the node is entered, in
+// front of the group record's LDS reads, and parked where the parent order fetched it: the L2 round trip runs under the box tests, the ballots
+// and the branch instead of behind them.  A node none of whose children is wanted drops the value (one L2-resident 512-byte line; no state
+// changes).  Every address issued lies inside the cloud's block whatever the node (address safety).  -DHGS_WALK_FETCH_ON_ENTRY=0
+// restores the former order (fetch where the quad is parked) in wave_nn1_quad, -DHGS_WALK_FETCH_KNN=0 in wave_walk_quad: A/B builds
+// (scripts/build_variant.sh); nothing is decided at run time.
+#ifndef HGS_WALK_FETCH_ON_ENTRY
+#define HGS_WALK_FETCH_ON_ENTRY 1
+#endif
+#ifndef HGS_WALK_FETCH_KNN
+#define HGS_WALK_FETCH_KNN 1
+#endif
+
+// A quad fetch in two halves.  Issue: lane l loads bytes 8l..8l+7 of the four records (512 contiguous bytes) starting at `quad`.
+__device__ __forceinline__ hgs_f2 quad_issue(const Float4* quad) {
   const int l = (int)(__lane_id() & 63u);
-  const hgs_f2 v = reinterpret_cast<const hgs_f2*>(quad)[l];
+  return reinterpret_cast<const hgs_f2*>(quad)[l];
+}
+// Park: the loaded pair -> LDS slot (this is where the wave waits for the load).
+__device__ __forceinline__ void quad_park(hgs_f2 v, float* slot) {
+  const int l = (int)(__lane_id() & 63u);
   __builtin_amdgcn_wave_barrier();  // earlier reads of this slot are issued before it is overwritten
   reinterpret_cast<hgs_f2*>(slot)[l] = v;
   __builtin_amdgcn_wave_barrier();
 }
+__device__ __forceinline__ void fetch_quad(const Float4* quad, float* slot) { quad_park(quad_issue(quad), slot); }
 
 __device__ __forceinline__ float nn1_exclusive_bound(float d2_inclusive) {
   const unsigned u = __float_as_uint(d2_inclusive) + 1u;  // next float up: "m < bound" == "m <= d2_inclusive"
@@ -339,15 +357,27 @@ struct QuadCursor {
   }
   __device__ __forceinline__ bool at_leaf_parent() const { return lvl == 1; }
   __device__ __forceinline__ unsigned first_child() const { return node << 2; }
-  // all four leaves below `node` with one fetch (slot 0)
+  // The load of the child quad of `node`, issued and not waited for: group records 4 node .. 4 node + 3 above level 1, the four leaves below a
+  // level-1 node.  The same addresses descend / fetch_leaf_quad fetch, known the moment the node is entered.  The load's only use sits in a
+  // conditional block (a node without a wanted child has none), where the optimiser would sink it: the empty asm keeps it in front of
+  // everything that follows in program order.
+  __device__ __forceinline__ hgs_f2 issue_children() const {
+    const hgs_f2 v = quad_issue((lvl > 1 ? nodes : leaves) + 8 * (size_t)first_child());
+    asm volatile("" ::: "memory");
+    return v;
+  }
+  // all four leaves below `node` (slot 0): with one fetch, or parked from the load issued on entry
   __device__ __forceinline__ void fetch_leaf_quad() const { fetch_quad(leaves + 8 * (size_t)first_child(), park); }
-  // enter child c of `node`; the other wanted children (any) stay pending.  The four child records arrive with one fetch.
-  __device__ __forceinline__ void descend(unsigned any, int c) {
+  __device__ __forceinline__ void park_leaf_quad(hgs_f2 children) const { quad_park(children, park); }
+  // enter child c of `node`; the other wanted children (any) stay pending.  The four child records arrive with one fetch — issued here, or on
+  // entry of `node` (`children`: what issue_children() returned for it).
+  __device__ __forceinline__ void descend(unsigned any, int c) { descend(any, c, quad_issue(nodes + 8 * (size_t)first_child())); }
+  __device__ __forceinline__ void descend(unsigned any, int c, hgs_f2 children) {
     lvl -= 1;
     pend |= (unsigned long long)(any & ~(1u << c)) << (4 * lvl);
     const unsigned base = first_child();
     float* s = slot(lvl);
-    fetch_quad(nodes + 8 * (size_t)base, s);
+    quad_park(children, s);
     node = base + (unsigned)c;
     rec = s + 32 * c;
   }
@@ -402,7 +432,7 @@ __device__ __forceinline__ void visit_leaf_quad(unsigned todo, int c, Wanted&& w
 }
 
 // TRACK: also keep the best leaf and the number of leaves that reached the minimum (what nn1_resolve_leaf needs)
-template <bool ORDERED, bool TRACK>
+template <bool ORDERED, bool TRACK, bool EARLY = (HGS_WALK_FETCH_ON_ENTRY != 0)>
 __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* kParkFloats, wave-private, 512-byte aligned */, const F3& q0, bool active,
                                               float bound2, int seed, int order_lane, float& best_out, int& leaf_out, bool& tie_out, bool& found_out) {
   const int k = 31 - __clz(t.P);
@@ -448,6 +478,8 @@ __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* k
     QuadCursor cur;
     cur.start(t, k, park);
     for (;;) {
+      hgs_f2 children = {0.f, 0.f};
+      if (EARLY) children = cur.issue_children();  // in flight under the group step below
       {  // the group of `node`: boxes of its four grandchildren  {mnx[4], mny[4], mnz[4], mxx[4]} {mxy[4], mxz[4]}
         const float* rec = cur.rec;
         const hgs_f16v lo = *reinterpret_cast<const hgs_f16v*>(rec);
@@ -467,11 +499,13 @@ __device__ __forceinline__ void wave_nn1_quad(const BvhView& t, float* park /* k
           if (p >= 0) cstar = p;
         }
         if (!cur.at_leaf_parent()) {
-          cur.descend(any, cstar);
+          if (EARLY) cur.descend(any, cstar, children);
+          else cur.descend(any, cstar);
           continue;
         }
         // the children are leaves: all four records with one fetch, visited in place
-        cur.fetch_leaf_quad();
+        if (EARLY) cur.park_leaf_quad(children);
+        else cur.fetch_leaf_quad();
         const unsigned base = cur.first_child();
         visit_leaf_quad(any, cstar, wanted, [&](int c) { visit_leaf(park + 32 * c, (int)(base + (unsigned)c)); });
       }
@@ -508,7 +542,7 @@ __device__ __forceinline__ void nn1_resolve_leaf(const BvhView& t, const F3& q, 
 // traversal as wave_walk_multi<Lane, 1> — nearest-first by the order lane, leaves of a leaf-parent group in place with the
 // bounds re-tested after every visit, pending children entered directly, the skip window, the leaf log — with the records
 // fetched four at a time and parked per level (fetch_quad): one memory wait per group that has wanted children.
-template <class Lane>
+template <class Lane, bool EARLY = (HGS_WALK_FETCH_KNN != 0)>
 __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, const F3& q, float* park /* kParkFloats */, int order_lane, unsigned skip_lo_ = 0,
                                                unsigned skip_n_ = 0, LeafLog* log = nullptr) {
   const int k = 31 - __clz(t.P);
@@ -548,6 +582,8 @@ __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, con
   cur.start(t, k, park);
   for (;;) {
     HGS_PROBE_COUNT(0);
+    hgs_f2 children = {0.f, 0.f};
+    if (EARLY) children = cur.issue_children();
     {
       const float* rec = cur.rec;
       const hgs_f16v lo = *reinterpret_cast<const hgs_f16v*>(rec);
@@ -567,7 +603,8 @@ __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, con
         if (p >= 0) cstar = p;
       }
       if (!cur.at_leaf_parent()) {
-        cur.descend(any, cstar);
+        if (EARLY) cur.descend(any, cstar, children);
+        else cur.descend(any, cstar);
         continue;
       }
       const unsigned base = cur.first_child();
@@ -577,7 +614,8 @@ __device__ __forceinline__ void wave_walk_quad(const BvhView& t, Lane& lane, con
           if (base + c - skip_lo < skip_n) todo &= ~(1u << c);  // leaves the caller has handled
       }
       if (todo) {
-        cur.fetch_leaf_quad();
+        if (EARLY) cur.park_leaf_quad(children);
+        else cur.fetch_leaf_quad();
         visit_leaf_quad(todo, (todo >> cstar) & 1u ? cstar : __builtin_ctz(todo), wanted, [&](int c) { visit(park + 32 * c, base + (unsigned)c); });
       }
     }

@@ -12,6 +12,7 @@ import dataclasses
 import hashlib
 import os
 import tempfile
+import threading
 
 import numpy as np
 
@@ -146,6 +147,7 @@ def scan(scene: Scene, sensor: str, pose: np.ndarray, noise_seed: int, noise_sig
     return out
 
 
+_MATMUL_LOCK = threading.Lock()  # _scan_uncached: one BLAS product at a time
 _SELF_DIGEST = None  # sha256 of this file, computed once per process (the cache key's "simulator version")
 
 
@@ -192,7 +194,12 @@ def _scan_uncached(scene: Scene, sensor: str, pose: np.ndarray, noise_seed: int,
     T = pose.copy()
     T[2, 3] += SENSORS[sensor][4]
     o = T[:3, 3]
-    d_w = dirs_s @ T[:3, :3].T
+    # The one BLAS call of a cast.  workloads._cast_scans casts several revolutions on host threads, and a threaded BLAS that is entered by two of them
+    # at once splits this product differently from a call that has the library to itself: the directions then differ in the last bit, a few returns move
+    # across the range gates below, and the "same" scan differs by a few points from run to run (seen as benchmark outputs that differ between two runs of
+    # one library in whole groups of candidates cut from one scan).  One product at a time: every scan is the sequential loop's, bit for bit.
+    with _MATMUL_LOCK:
+        d_w = dirs_s @ T[:3, :3].T
     t = _cast(scene, o, d_w, max_range)
     rng = np.random.default_rng(noise_seed)
     t = t + rng.normal(0.0, noise_sigma, size=t.shape)
