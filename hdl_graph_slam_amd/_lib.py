@@ -118,6 +118,7 @@ EXPORTS = [
     "hgs_floor_params_default", "hgs_detect_floor", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
     "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_vgicp_voxels", "hgs_debug_cloud_seed_grid", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
+    "hgs_debug_lane_plan", "hgs_debug_plan_lanes", "hgs_debug_batch_order",
 ]
 
 _lib = None
@@ -178,6 +179,9 @@ def lib():
     L.hgs_synchronize.argtypes = [vp]
     L.hgs_debug_target_covariances.argtypes = [vp, vp]
     L.hgs_debug_set_option.argtypes = [vp, C.c_char_p, C.c_int32]
+    L.hgs_debug_lane_plan.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hgs_debug_plan_lanes.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.hgs_debug_batch_order.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]
     L.hgs_debug_gicp_linearize.argtypes = [vp, vp, vp, vp, vp, vp]
     L.hgs_debug_icp_correspond.argtypes = [vp, vp, vp, vp]
     L.hgs_debug_icp_step.argtypes = [vp, vp, vp, C.c_double, C.c_int32, vp, vp, vp]

@@ -148,7 +148,7 @@ void launch_fitness(hipStream_t s, const CloudDesc* descs, const TargetView* tvi
 }  // namespace hgs
 struct hgs_result;  // include/hgs_registration.h
 namespace hgs {
-void launch_results_to_records(hipStream_t s, const DevResult* res, const int* candidate_ids, int n, int n_slots, ::hgs_result* out);
+void launch_results_to_records(hipStream_t s, const DevResult* res, const int* candidate_ids, const int* pos, int n, int n_slots, ::hgs_result* out);
 void launch_nn_query(hipStream_t s, TargetView tgt, const float4* q, int nq, int* idx, float* d2);
 // seed grid of a target cloud: every sorted point enters three direct-mapped tables (cells of 0.25 / 1 / 4 m, sizes 2^bits, 2^(bits-2), 2^(bits-4))
 void launch_seed_grid_build(hipStream_t s, const float4* pts, const CloudMeta* meta, int n_max, unsigned* tab, int bits);

@@ -103,6 +103,14 @@ struct hgs_handle {
   // block-per-problem solve / decide kernels of one lane run under the point kernels of the others
   hipStream_t lane_stream[7] = {};  // kMaxLanes - 1
   hipEvent_t lane_event[8] = {};
+  // Ordered lanes (run_batch, FAST_GICP / FAST_VGICP from 8 problems up, DESIGN.md "Ordered lanes"): the half of a batch whose guesses lie farthest from the
+  // target (likely the slowest to converge) runs on highest-priority streams, so that its short late rounds are dispatched ahead of the other half's big
+  // grids instead of in lock-step with them.  0: contiguous lanes of equal priority.  "lane_order" (hgs_debug_set_option).  64 x 119 k batch, alternating with
+  // the parent library, five runs each: 5907.7 - 5979.7 -> 6149.5 - 6209.7 registrations/s (profiles/lane_order_ab_bench.md)
+  int lane_order = 1;
+  hipStream_t prio_stream[2] = {};  // created on first use (open_lanes), counted against the queue budget like lane_stream, destroyed with them
+  std::vector<int> batch_order;     // internal position -> caller's position of the batch whose records sit in `results`; empty: the caller's order
+  int last_lanes = 0, last_ahead_lanes = 0;  // the lane plan of the last batch (hgs_debug_lane_plan)
   int lane_start = 1;                // 1: the host synchronises before it releases the lanes of a batch (open_lanes); HGS_LANE_START=0: not (A/B runs)
   int nn_qpw = 0;  // queries per packet of k_gicp_linearize in the two-launch LM rounds: 0 = by launch size (run_batch), 16 / 32 / 64
   int nn_qpw16_below = 96, nn_qpw32_below = 0;  // ... 16 up to this many 256-point tiles in the launch, 32 up to that many
@@ -198,6 +206,8 @@ struct hgs_handle {
   void synchronize_streams() {
     if (stream) (void)hipStreamSynchronize(stream);
     for (hipStream_t ls : lane_stream)
+      if (ls) (void)hipStreamSynchronize(ls);
+    for (hipStream_t ls : prio_stream)
       if (ls) (void)hipStreamSynchronize(ls);
   }
   ~hgs_handle();
@@ -813,10 +823,13 @@ struct BatchLane {
   bool finished = false;
 };
 
-// Splits B problems into lanes (contiguous ranges) and makes the extra streams wait for what the main stream has enqueued
-// so far (indices, covariances, descriptors, guesses).  Profiling keeps one lane: the stage timers bracket launches on the
-// main stream and are meant to time kernels that have the device to themselves.
-int open_lanes(hgs_handle* h, int B, size_t partial_bytes_per_problem, size_t partial_err_bytes_per_problem, std::vector<BatchLane>& lanes, int tiles_per_problem) {
+// How many lanes a batch of B problems opens (`lanes`), and how many of them run the ahead group on priority streams (`ahead`; 0: contiguous lanes of equal
+// priority).  ordered: the caller has sorted the problems for ordered lanes (run_batch) — granted only where more than one lane opens anyway.
+struct LanePlan {
+  int lanes, ahead;
+};
+// assume_streams >= 0 (hgs_debug_plan_lanes): plan as if the process held that many streams on the device instead of the counted ones.
+LanePlan plan_lanes(hgs_handle* h, int B, int tiles_per_problem, bool ordered, int assume_streams = -1) {
   // round 3, 64 x 119 k FAST_GICP batch: 1 / 2 / 3 / 4 lanes = 5615 / 5755 / 5787 / 5811 registrations/s (round 2's kernels preferred 2 above 32 problems)
   // NDT (one launch per iteration, work queue inside): 2 / 3 / 4 lanes = 1679 / 1724 / 1652 on the 64-candidate batch (round 2: 1403 / 1384 / 1326)
   // round 6, batches of SMALL problems (candidate keyframes of a KITTI run: prefiltered sweeps of 11-14 k points; scripts/probes/small_batch_lanes_probe.py,
@@ -829,31 +842,69 @@ int open_lanes(hgs_handle* h, int B, size_t partial_bytes_per_problem, size_t pa
   int n = h->profiling ? 1 : std::max(1, std::min(std::min(wanted, kMaxLanes), B));  // (h_flags / done hold 2 ints per lane: 64 bytes = 8 lanes)
   // the process's hardware-queue budget (above): lane streams this engine already owns are free, new ones only while there is room.
   // HGS_BATCH_LANES (A/B runs) overrides the budget.
-  if (h->batch_lanes <= 0) {
-    int owned = 0;
-    while (owned < kMaxLanes - 1 && h->lane_stream[owned]) owned++;
-    const int room = std::max(0, hw_queue_budget() - streams_in_use(h->device).load(std::memory_order_relaxed));
-    n = std::min(n, 1 + owned + room);
-  }
+  int owned = 0, owned_prio = 0;
+  while (owned < kMaxLanes - 1 && h->lane_stream[owned]) owned++;
+  while (owned_prio < 2 && h->prio_stream[owned_prio]) owned_prio++;
+  const int room = std::max(0, hw_queue_budget() - (assume_streams >= 0 ? assume_streams : streams_in_use(h->device).load(std::memory_order_relaxed)));
+  const int plain = h->batch_lanes <= 0 ? std::min(n, 1 + owned + room) : n;
+  if (!ordered || h->profiling || plain < 2) return LanePlan{plain, 0};
+  // ordered lanes: four lanes = two ahead (priority streams) + two crowd (the engine's own stream and one more), three = 1 + 2, two = 1 + 1.  The
+  // priority streams are streams like any other to the budget: the largest plan whose NEW streams the budget has room for — and if that is fewer
+  // lanes than the plain plan opens (an engine that owns plain lane streams in a process whose budget is spent), the plain plan stands
+  n = std::min(n, 4);
+  auto ahead_of = [](int lanes) { return lanes >= 4 ? 2 : 1; };
+  if (h->batch_lanes <= 0)
+    while (n > 1 && std::max(0, ahead_of(n) - owned_prio) + std::max(0, n - ahead_of(n) - 1 - owned) > room) n--;
+  if (n < 2 || n < std::min(plain, 4)) return LanePlan{plain, 0};
+  return LanePlan{n, ahead_of(n)};
+}
+
+// highest-priority, non-blocking; the host emulation of the kernels has no stream priorities: a plain stream there
+hipError_t create_priority_stream(hipStream_t* out) {
+#ifdef HGS_SIMT_EMULATION
+  return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+#else
+  int least = 0, greatest = 0;
+  const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+  if (e != hipSuccess) return e;
+  return hipStreamCreateWithPriority(out, hipStreamNonBlocking, greatest);
+#endif
+}
+
+// Splits B problems into lanes (contiguous ranges) and makes the extra streams wait for what the main stream has enqueued
+// so far (indices, covariances, descriptors, guesses).  Profiling keeps one lane: the stage timers bracket launches on the
+// main stream and are meant to time kernels that have the device to themselves.
+// ahead_problems > 0: the caller has put the batch's ahead group in front (run_batch: problems [0, ahead_problems)); the plan's ahead lanes share it, the
+// other lanes the rest.  The lane on the engine's own stream is then not the first of the list — nothing but close_lanes cared.
+int open_lanes(hgs_handle* h, int B, size_t partial_bytes_per_problem, size_t partial_err_bytes_per_problem, std::vector<BatchLane>& lanes, int tiles_per_problem,
+               int ahead_problems = 0) {
+  const LanePlan plan = plan_lanes(h, B, tiles_per_problem, ahead_problems > 0);
+  const int n = plan.lanes;
+  h->last_lanes = n, h->last_ahead_lanes = plan.ahead;
   lanes.assign(n, BatchLane{});
-  for (int i = 0, b0 = 0; i < n; i++) {
+  for (int i = 0, b0 = 0, extra = 0; i < n; i++) {
     BatchLane& L = lanes[i];
-    L.b0 = b0, L.B = (B - b0) / (n - i);
+    const bool ahead = i < plan.ahead;
+    // (without ahead lanes: one group of all B problems over all n lanes)
+    const int group_end = plan.ahead == 0 ? B : (ahead ? ahead_problems : B), group_lanes_left = plan.ahead == 0 ? n - i : (ahead ? plan.ahead - i : n - i);
+    L.b0 = b0, L.B = (group_end - b0) / group_lanes_left;
     b0 += L.B;
     HGS_TRY(make_progress(h, i, L.B, &L.prog));
-    if (i == 0) {
+    if (i == plan.ahead) {  // the first lane that is not ahead: the engine's own stream and buffers
       L.stream = h->stream;
       L.partials = h->partials.as<double>(), L.partials_err = h->partials_err.as<double>();
       continue;
     }
-    if (!h->lane_stream[i - 1]) {
-      HGS_HIP(h, hipStreamCreateWithFlags(&h->lane_stream[i - 1], hipStreamNonBlocking));
+    hipStream_t& ls = ahead ? h->prio_stream[i] : h->lane_stream[i - plan.ahead - 1];
+    if (!ls) {
+      HGS_HIP(h, ahead ? create_priority_stream(&ls) : hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
       streams_in_use(h->device).fetch_add(1, std::memory_order_relaxed);
     }
-    L.stream = h->lane_stream[i - 1];
-    HGS_HIP(h, h->lane_partials[i - 1].reserve((size_t)L.B * partial_bytes_per_problem));
-    HGS_HIP(h, h->lane_partials_err[i - 1].reserve((size_t)L.B * partial_err_bytes_per_problem));
-    L.partials = h->lane_partials[i - 1].as<double>(), L.partials_err = h->lane_partials_err[i - 1].as<double>();
+    L.stream = ls;
+    HGS_HIP(h, h->lane_partials[extra].reserve((size_t)L.B * partial_bytes_per_problem));
+    HGS_HIP(h, h->lane_partials_err[extra].reserve((size_t)L.B * partial_err_bytes_per_problem));
+    L.partials = h->lane_partials[extra].as<double>(), L.partials_err = h->lane_partials_err[extra].as<double>();
+    extra++;
   }
   if (n > 1) {
     // Round 5 removed the host synchronisations behind the index build and the covariance pass (they only protected a pinned staging buffer: PinnedRing).
@@ -865,17 +916,20 @@ int open_lanes(hgs_handle* h, int B, size_t partial_bytes_per_problem, size_t pa
     if (h->lane_start != 0) HGS_HIP(h, hipStreamSynchronize(h->stream));
     if (!h->lane_event[0]) HGS_HIP(h, hipEventCreateWithFlags(&h->lane_event[0], hipEventDisableTiming));
     HGS_HIP(h, hipEventRecord(h->lane_event[0], h->stream));
-    for (int i = 1; i < n; i++) HGS_HIP(h, hipStreamWaitEvent(lanes[i].stream, h->lane_event[0], 0));
+    for (BatchLane& L : lanes)
+      if (L.stream != h->stream) HGS_HIP(h, hipStreamWaitEvent(L.stream, h->lane_event[0], 0));
   }
   return HGS_OK;
 }
 
 // The main stream continues after every lane has finished.
 int close_lanes(hgs_handle* h, std::vector<BatchLane>& lanes) {
-  for (size_t i = 1; i < lanes.size(); i++) {
-    if (!h->lane_event[i]) HGS_HIP(h, hipEventCreateWithFlags(&h->lane_event[i], hipEventDisableTiming));
-    HGS_HIP(h, hipEventRecord(h->lane_event[i], lanes[i].stream));
-    HGS_HIP(h, hipStreamWaitEvent(h->stream, h->lane_event[i], 0));
+  for (size_t i = 0; i < lanes.size(); i++) {
+    if (lanes[i].stream == h->stream) continue;
+    const size_t ev = i == 0 ? lanes.size() : i;  // (lane_event[0] is open_lanes'; ordered lanes: lane 0 is an ahead lane and at most 4 lanes open)
+    if (!h->lane_event[ev]) HGS_HIP(h, hipEventCreateWithFlags(&h->lane_event[ev], hipEventDisableTiming));
+    HGS_HIP(h, hipEventRecord(h->lane_event[ev], lanes[i].stream));
+    HGS_HIP(h, hipStreamWaitEvent(h->stream, h->lane_event[ev], 0));
   }
   return HGS_OK;
 }
@@ -988,7 +1042,8 @@ void lane_fitness_tail(hgs_handle* h, BatchLane& L, const BatchShape& s, const d
 }
 
 // The rounds of a FAST_GICP / FAST_VGICP batch.  guess_in_args: a single GICP registration, whose guess rides in k_gicp_init1's arguments.
-int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_host, bool guess_in_args, const double* fit_max_range) {
+// ahead_problems: run_batch has sorted the problems for ordered lanes, the first that many are the ahead group (open_lanes); 0: not.
+int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_host, bool guess_in_args, const double* fit_max_range, int ahead_problems = 0) {
   const int B = s.B, max_blocks = s.max_blocks;
   hgs_cloud* tgt = h->target;
   const bool voxel = h->prm.method == HGS_FAST_VGICP;
@@ -1010,7 +1065,7 @@ int run_gicp_rounds(hgs_handle* h, const BatchShape& s, const float* guesses_hos
   const NdtTargetView vtv = voxel && !s.d_vviews ? vgicp_target_view(tgt) : NdtTargetView{};  // (run_pair_batch: one voxel map per problem, on the device)
   const long max_rounds = (long)std::max(1, c.max_iterations) * std::max(1, c.lm_max_iterations) + 2 + (round2 ? 1 : 0);  // (round2: a round's accept / reject runs in the next round's first kernel)
   std::vector<BatchLane> lanes;
-  HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccNdt * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks));
+  HGS_TRY(open_lanes(h, B, (size_t)max_blocks * kAccNdt * sizeof(double), (size_t)max_blocks * 2 * sizeof(double), lanes, s.err_blocks, ahead_problems));
   auto finish_lane = [&](BatchLane& L) {
     if (early && *L.prog.host_done) {  // (not when the lane ran out of rounds: then the result kernel + copy below fetch whatever state it is in)
       h->early_valid = true;
@@ -1191,12 +1246,29 @@ int run_ndt_rounds(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const 
   return close_lanes(h, lanes);
 }
 
+// Ordered lanes: the order a batch runs in.  The hint of a problem is the squared translation norm of its guess (elements 12, 13, 14 of the column-major
+// 4x4; a non-finite one counts as FLT_MAX, so the comparison stays a strict weak order): a candidate far from the query overlaps it less and converges
+// slower (DESIGN.md "Ordered lanes").  Stable, descending: order[i] = the caller's position of the problem that runs i-th.
+constexpr int kLaneOrderMinProblems = 8;
+void lane_order_of(const float* guesses, int B, std::vector<int>& order) {
+  std::vector<float> hint(B);
+  for (int b = 0; b < B; b++) {
+    const float* t = guesses + (size_t)b * 16 + 12;
+    const float d2 = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
+    hint[b] = std::isfinite(d2) ? d2 : FLT_MAX;
+  }
+  order.resize(B);
+  for (int b = 0; b < B; b++) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hint[a] > hint[b]; });
+}
+
 // Run all B registrations (sources vs the handle's target) to completion; results land in h->results (device).
 // With fit_max_range the getFitnessScore pass of every problem (fit_sum / fit_count of its result record) is enqueued on
 // the problem's lane as soon as the lane has converged, i.e. under the remaining iterations of the other lanes.
 int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float* guesses_host, const double* fit_max_range = nullptr) {
   const int B = (int)sources.size();
   h->early_valid = false;
+  h->batch_order.clear();
   hgs_cloud* tgt = h->target;
   const int method = h->prm.method;
   const bool gicp = method == HGS_FAST_GICP || method == HGS_FAST_VGICP;
@@ -1219,15 +1291,35 @@ int run_batch(hgs_handle* h, const std::vector<hgs_cloud*>& sources, const float
     HGS_TRY(ensure_ndt_target(h, tgt));
   }
   if (fit_max_range && method != HGS_FAST_GICP) HGS_TRY(ensure_seed_grid(h, tgt));  // getFitnessScore without correspondences to start from (k_fitness)
+  // Ordered lanes (hgs_handle::lane_order): the batch runs in an internal order, farthest guess first, whose first half goes to the ahead lanes.  From here to
+  // fetch_results / k_results_to_records everything per problem (descriptors, guesses, states, records, partial sums) is in that order; a record does not
+  // depend on where or when its problem runs, so the hint, however wrong, changes no bit of it.
+  std::vector<hgs_cloud*> ordered_sources;
+  std::vector<float> ordered_guesses;
+  int ahead_problems = 0;
+  if (gicp && h->lane_order && B >= kLaneOrderMinProblems) {
+    int max_n = 0;
+    for (hgs_cloud* c : sources) max_n = std::max(max_n, (int)c->n_input);
+    if (plan_lanes(h, B, std::max(1, (max_n + kBlock - 1) / kBlock) /* BatchShape::err_blocks */, true).ahead > 0) {
+      lane_order_of(guesses_host, B, h->batch_order);
+      ordered_sources.resize(B), ordered_guesses.resize((size_t)B * 16);
+      for (int i = 0; i < B; i++) {
+        ordered_sources[i] = sources[h->batch_order[i]];
+        std::memcpy(&ordered_guesses[(size_t)i * 16], guesses_host + (size_t)h->batch_order[i] * 16, 16 * sizeof(float));
+      }
+      guesses_host = ordered_guesses.data();
+      ahead_problems = (B + 1) / 2;
+    }
+  }
   BatchShape s;
-  HGS_TRY(batch_shape(h, sources, true, &s));
+  HGS_TRY(batch_shape(h, ahead_problems ? ordered_sources : sources, true, &s));
   const bool guess_in_args = B == 1 && method == HGS_FAST_GICP;  // (a single GICP registration: the guess rides in k_gicp_init1's arguments)
   HGS_HIP(h, h->guesses.reserve((size_t)B * 16 * sizeof(float)));
   if (!guess_in_args) HGS_HIP(h, h->up.upload(h->guesses.p, guesses_host, (size_t)B * 16 * sizeof(float), h->stream));  // (the caller's array is pageable: through a pinned slot)
   HGS_HIP(h, h->results.reserve((size_t)B * sizeof(DevResult)));
   HGS_HIP(h, h->partials.reserve((size_t)B * s.max_blocks * kAccNdt * sizeof(double)));
   HGS_HIP(h, h->partials_err.reserve((size_t)B * s.max_blocks * 2 * sizeof(double)));
-  if (gicp) HGS_TRY(run_gicp_rounds(h, s, guesses_host, guess_in_args, fit_max_range));
+  if (gicp) HGS_TRY(run_gicp_rounds(h, s, guesses_host, guess_in_args, fit_max_range, ahead_problems));
   else if (method == HGS_ICP) HGS_TRY(run_icp_rounds(h, s, fit_max_range));
   else HGS_TRY(run_ndt_rounds(h, sources, s, fit_max_range));
   HGS_HIP(h, hipGetLastError());
@@ -1247,6 +1339,7 @@ int run_group_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const
   const int B = (int)sources.size();
   const int method = h->prm.method;
   h->early_valid = false;
+  h->batch_order.clear();
   std::vector<hgs_cloud*> all(sources);
   all.insert(all.end(), targets.begin(), targets.end());
   if (method == HGS_FAST_GICP) HGS_TRY(ensure_cov(h, all, h->prm.correspondence_randomness));
@@ -1294,6 +1387,7 @@ int run_pair_batch(hgs_handle* h, const std::vector<hgs_cloud*>& targets, const 
   const int B = (int)sources.size();
   const bool voxel = method == HGS_FAST_VGICP;
   h->early_valid = false;
+  h->batch_order.clear();
   std::vector<hgs_cloud*> all(sources);
   all.insert(all.end(), targets.begin(), targets.end());
   std::vector<hgs_cloud*> distinct;  // targets, in order of first appearance
@@ -1371,6 +1465,8 @@ int fetch_results(hgs_handle* h, int B, std::vector<DevResult>& out) {
   HGS_HIP(h, hipMemcpyAsync(h->h_results.p, h->results.p, (size_t)B * sizeof(DevResult), hipMemcpyDeviceToHost, h->stream));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
   out.assign(h->h_results.as<DevResult>(), h->h_results.as<DevResult>() + B);
+  if ((int)h->batch_order.size() == B)  // an ordered batch (run_batch): back to the caller's order
+    for (int i = 0; i < B; i++) out[h->batch_order[i]] = h->h_results.as<DevResult>()[i];
   return HGS_OK;
 }
 
@@ -1403,6 +1499,7 @@ int run_pair_fitness(hgs_handle* h, hgs_cloud* const* cloud1, hgs_cloud* const* 
     std::memset(poses.data(), 0, B * sizeof(DevResult));
     for (size_t b = 0; b < B; b++) std::memcpy(poses[b].T, relposes + 16 * (p0 + b), sizeof(float) * 16);
     HGS_HIP(h, h->results.reserve(B * sizeof(DevResult)));
+    h->batch_order.clear();
     HGS_HIP(h, h->up.upload(h->results.p, poses.data(), B * sizeof(DevResult), h->stream));
     HGS_HIP(h, h->partials_err.reserve(B * s.max_blocks * 2 * sizeof(double)));
     BatchLane whole;  // every pair of the chunk on the engine's stream
@@ -1434,6 +1531,7 @@ void to_public(const DevResult& d, int candidate, bool with_fitness, hgs_result*
 }
 
 int upload_pose_as_result(hgs_handle* h, const float T[16]) {
+  h->batch_order.clear();
   HGS_HIP(h, h->results.reserve(sizeof(DevResult)));
   HGS_HIP(h, h->h_results.reserve(sizeof(DevResult)));
   DevResult* r = h->h_results.as<DevResult>();
@@ -1502,6 +1600,8 @@ hgs_handle::~hgs_handle() {
     for (const ProfEvent& ev : *list) (void)hipEventDestroy(ev.a), (void)hipEventDestroy(ev.b);
   for (hipStream_t ls : lane_stream)
     if (ls) (void)hipStreamDestroy(ls), streams_in_use(device).fetch_sub(1, std::memory_order_relaxed);  // (counted where each was created: open_lanes,
+  for (hipStream_t ls : prio_stream)
+    if (ls) (void)hipStreamDestroy(ls), streams_in_use(device).fetch_sub(1, std::memory_order_relaxed);
   if (stream) (void)hipStreamDestroy(stream), streams_in_use(device).fetch_sub(1, std::memory_order_relaxed);  //  hgs_create)
 }
 
@@ -1519,6 +1619,7 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
   const std::string k(key);
   if (k == "batch_lanes") h->batch_lanes = value <= 0 ? 0 : std::min(kMaxLanes, value);                  // 0: open_lanes chooses
   else if (k == "lane_start") h->lane_start = value != 0 ? 1 : 0;
+  else if (k == "lane_order") h->lane_order = value != 0 ? 1 : 0;
   else if (k == "ndt_sort") h->ndt_sort = std::max(-1, std::min(1, value));
   else if (k == "cov_split") h->cov_split = value != 0 ? 1 : 0;
   else if (k == "fused_rounds") h->fused_rounds = value != 0 ? 1 : 0;
@@ -1546,6 +1647,38 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
     h->err = "hgs_debug_set_option: unknown option '" + k + "'";
     return HGS_ERR_INVALID_ARGUMENT;
   }
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_lane_plan(hgs_handle* h, int32_t* lanes, int32_t* ahead_lanes, int32_t* process_streams) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (lanes) *lanes = h->last_lanes;
+  if (ahead_lanes) *ahead_lanes = h->last_ahead_lanes;
+  if (process_streams) *process_streams = streams_in_use(h->device).load(std::memory_order_relaxed);
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_plan_lanes(hgs_handle* h, int32_t n_problems, int32_t tiles_per_problem, int32_t ordered, int32_t assume_streams, int32_t* lanes, int32_t* ahead_lanes) try {
+  ApiLock lock(h);
+  if (!h || n_problems < 1) return HGS_ERR_INVALID_ARGUMENT;
+  const LanePlan plan = plan_lanes(h, n_problems, tiles_per_problem, ordered != 0 && h->lane_order && n_problems >= kLaneOrderMinProblems, assume_streams);
+  if (lanes) *lanes = plan.lanes;
+  if (ahead_lanes) *ahead_lanes = plan.ahead;
+  return HGS_OK;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+int hgs_debug_batch_order(hgs_handle* h, int32_t* order, int32_t cap, int32_t* n) try {
+  ApiLock lock(h);
+  if (!h || !n || cap < 0 || (cap > 0 && !order)) return HGS_ERR_INVALID_ARGUMENT;
+  *n = (int32_t)h->batch_order.size();
+  for (int32_t i = 0; i < std::min(cap, *n); i++) order[i] = h->batch_order[i];
   return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
@@ -2197,12 +2330,12 @@ int hgs_loop_match_batch_sharded(hgs_handle* h, hgs_cloud* const* candidates, si
   const size_t n_send = local == HGS_OK ? n_mine : 0;
   // ---- exchange buffers (persistent, worst case: one rank holds every candidate)
   const size_t hdr_bytes = 16;
-  const size_t ids_off = align_up((size_t)world * hdr_bytes + hdr_bytes, 16), rec_off = align_up(ids_off + n_total * sizeof(int32_t), 16);
+  const size_t ids_off = align_up((size_t)world * hdr_bytes + hdr_bytes, 16), rec_off = align_up(ids_off + 2 * n_total * sizeof(int32_t), 16);  // (ids: the candidate ids, and behind them where each slot's record sits in h->results)
   bool mem_ok = set_device(h) == HGS_OK;
   mem_ok = mem_ok && h->results.reserve(std::max<size_t>(n_total, 1) * sizeof(DevResult)) == hipSuccess;
   mem_ok = mem_ok && h->comm_send.reserve(n_total * sizeof(hgs_result) + hdr_bytes) == hipSuccess;
   mem_ok = mem_ok && h->comm_recv.reserve((size_t)world * (n_total * sizeof(hgs_result) + hdr_bytes)) == hipSuccess;
-  mem_ok = mem_ok && h->comm_ids.reserve(n_total * sizeof(int32_t)) == hipSuccess;
+  mem_ok = mem_ok && h->comm_ids.reserve(2 * n_total * sizeof(int32_t)) == hipSuccess;
   mem_ok = mem_ok && h->h_comm.reserve(rec_off + (size_t)world * n_total * sizeof(hgs_result)) == hipSuccess;
   if (!mem_ok) {
     hgs::comm_abort(h->comm);
@@ -2271,11 +2404,17 @@ int hgs_loop_match_batch_sharded(hgs_handle* h, hgs_cloud* const* candidates, si
     return HGS_ERR_HIP;
   }
   hgs_result* d_records = reinterpret_cast<hgs_result*>(d_send + hdr_bytes);
+  // an ordered batch (run_batch) left its records in its internal order: slot i (the caller's candidate i, with candidate_ids[i]) reads record pos[i]
+  const bool ordered = n_valid > 0 && h->batch_order.size() == n_valid;
   if (n_valid > 0) {
-    std::memcpy(static_cast<char*>(h->h_comm.p) + ids_off, candidate_ids, n_valid * sizeof(int32_t));
-    if (hipMemcpyAsync(h->comm_ids.p, static_cast<char*>(h->h_comm.p) + ids_off, n_valid * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) n_valid = 0;
+    int32_t* h_ids = reinterpret_cast<int32_t*>(static_cast<char*>(h->h_comm.p) + ids_off);
+    std::memcpy(h_ids, candidate_ids, n_valid * sizeof(int32_t));
+    if (ordered)
+      for (size_t i = 0; i < n_valid; i++) h_ids[n_valid + (size_t)h->batch_order[i]] = (int32_t)i;
+    if (hipMemcpyAsync(h->comm_ids.p, h_ids, (ordered ? 2 : 1) * n_valid * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) n_valid = 0;
   }
-  launch_results_to_records(h->stream, h->results.as<DevResult>(), h->comm_ids.as<int>(), (int)n_valid, (int)per, d_records);  // padding beyond n_valid
+  launch_results_to_records(h->stream, h->results.as<DevResult>(), h->comm_ids.as<int>(), ordered && n_valid > 0 ? h->comm_ids.as<int>() + n_valid : nullptr, (int)n_valid,
+                            (int)per, d_records);  // padding beyond n_valid
   hgs_result* d_gathered = reinterpret_cast<hgs_result*>(d_recv + (size_t)world * hdr_bytes);
   if (hgs::comm_all_gather(h->comm, d_records, d_gathered, per * sizeof(hgs_result), h->stream, err, sizeof(err)) != 0) {
     guard.armed = false;  // comm_failed aborts

@@ -1541,12 +1541,14 @@ void launch_fitness_final(hipStream_t s, const CloudDesc* descs, const double* p
 
 // DevResult -> the public per-candidate record (hgs_result, include/hgs_registration.h), written where the all-gather of a
 // sharded batch sends from: slot s < n_slots, padded with candidate_id -1 records beyond this rank's n candidates.
-__global__ void k_results_to_records(const DevResult* __restrict__ res, const int* __restrict__ candidate_ids, int n, int n_slots, hgs_result* __restrict__ out) {
+// pos (null: slot s reads res[s]): where slot s's record sits in res (a batch that ran in an order of its own, run_batch)
+__global__ void k_results_to_records(const DevResult* __restrict__ res, const int* __restrict__ candidate_ids, const int* __restrict__ pos, int n, int n_slots,
+                                     hgs_result* __restrict__ out) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_slots) return;
   hgs_result r;
   if (s < n) {
-    const DevResult d = res[s];
+    const DevResult d = res[pos ? pos[s] : s];
 #pragma unroll
     for (int k = 0; k < 16; k++) r.final_transformation[k] = d.T[k];
     r.converged = d.converged, r.iterations = d.iterations;
@@ -1562,9 +1564,9 @@ __global__ void k_results_to_records(const DevResult* __restrict__ res, const in
   }
   out[s] = r;
 }
-void launch_results_to_records(hipStream_t s, const DevResult* res, const int* candidate_ids, int n, int n_slots, hgs_result* out) {
+void launch_results_to_records(hipStream_t s, const DevResult* res, const int* candidate_ids, const int* pos, int n, int n_slots, hgs_result* out) {
   if (n_slots <= 0) return;
-  hipLaunchKernelGGL(k_results_to_records, dim3((n_slots + 63) / 64), dim3(64), 0, s, res, candidate_ids, n, n_slots, out);
+  hipLaunchKernelGGL(k_results_to_records, dim3((n_slots + 63) / 64), dim3(64), 0, s, res, candidate_ids, pos, n, n_slots, out);
 }
 
 __global__ __launch_bounds__(kBlock) void k_nn_query(TargetView tgt, const float4* __restrict__ q, int nq, int* __restrict__ idx, float* __restrict__ d2out) {

@@ -104,6 +104,26 @@ class RegistrationHIP:
     def set_option(self, key: str, value: int):
         self._check(L.lib().hgs_debug_set_option(self._h, key.encode(), int(value)))
 
+    def lane_plan(self):
+        """(lanes, ahead lanes) of the engine's last batch and the streams all engines of this process hold on its device (hgs_debug_lane_plan)."""
+        lanes, ahead, streams = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(L.lib().hgs_debug_lane_plan(self._h, C.byref(lanes), C.byref(ahead), C.byref(streams)))
+        return lanes.value, ahead.value, streams.value
+
+    def plan_lanes(self, n_problems: int, tiles_per_problem: int, ordered: bool = True, assume_streams: int = -1):
+        """(lanes, ahead lanes) a batch of that shape would get on this engine as it is now (hgs_debug_plan_lanes); nothing runs."""
+        lanes, ahead = C.c_int32(), C.c_int32()
+        self._check(L.lib().hgs_debug_plan_lanes(self._h, int(n_problems), int(tiles_per_problem), int(bool(ordered)), int(assume_streams), C.byref(lanes), C.byref(ahead)))
+        return lanes.value, ahead.value
+
+    def batch_order(self):
+        """Caller positions in the order the last loop-match batch ran in; empty: the caller's order (hgs_debug_batch_order)."""
+        n = C.c_int32()
+        self._check(L.lib().hgs_debug_batch_order(self._h, None, 0, C.byref(n)))
+        buf = (C.c_int32 * max(1, n.value))()
+        self._check(L.lib().hgs_debug_batch_order(self._h, buf, n.value, C.byref(n)))
+        return list(buf[:n.value])
+
     # ---- life cycle
     def close(self):
         if self._h:

@@ -449,7 +449,21 @@ int hgs_debug_ndt_derivatives(hgs_handle* h, const double p6[6], double* score, 
  * *duplicate_id = an id reported more than once (first report kept) or -1.  Needs no device: callable on a CPU-only box. */
 int hgs_debug_merge_shard_records(const hgs_result* gathered, const int32_t* counts, int32_t world, size_t per, size_t n_total,
                                   hgs_result* all_out, int32_t* duplicate_id);
-/* A measurement / test knob of one engine: "batch_lanes", "lane_start", "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
+/* The lane plan of the engine's last batch of LM / Newton rounds: *lanes = the streams its problems were spread over, *ahead_lanes = how many of them were
+ * highest-priority streams running the ahead group ("lane_order"; 0: contiguous lanes of equal priority), *process_streams = the streams all engines of this
+ * process hold on the engine's device right now, which is what the hardware-queue budget (GPU_MAX_HW_QUEUES, default 4) is compared with.  Any pointer may
+ * be NULL.  An additive debug symbol. */
+int hgs_debug_lane_plan(hgs_handle* h, int32_t* lanes, int32_t* ahead_lanes, int32_t* process_streams);
+/* The plan a batch of n_problems problems of tiles_per_problem 256-point tiles each WOULD get on this engine as it is now (its options, the streams it
+ * already owns), without running anything: ordered != 0 asks for ordered lanes as a FAST_GICP batch does ("lane_order", 8 problems or more).  assume_streams
+ * >= 0 plans against that many streams held by the process on the device instead of the counted ones (the budget arithmetic, testable without other
+ * engines); < 0: the counted ones.  Pure host code.  An additive debug symbol. */
+int hgs_debug_plan_lanes(hgs_handle* h, int32_t n_problems, int32_t tiles_per_problem, int32_t ordered, int32_t assume_streams, int32_t* lanes, int32_t* ahead_lanes);
+/* The order the engine's last hgs_loop_match_batch[_sharded] ran in: *n = its length (0: the caller's order, no ordered lanes), order[i] = the caller's
+ * position of the problem that ran i-th, the first min(cap, *n) entries.  The first (*n + 1) / 2 are the ahead group.  An additive debug symbol. */
+int hgs_debug_batch_order(hgs_handle* h, int32_t* order, int32_t cap, int32_t* n);
+/* A measurement / test knob of one engine: "batch_lanes", "lane_start", "lane_order" (1: a FAST_GICP / FAST_VGICP batch of 8 or more problems that opens
+ * several lanes runs the half whose guesses lie farthest from the target on highest-priority streams; records are handed back in the caller's order), "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
  * "seed_grid", "knn_replay", "ndt_resident", "ndt_chunk", "hilbert_levels", "nn_qpw", "nn_qpw16_below", "nn_qpw32_below", "fused_rounds", "fused_rounds_below", "fused_rounds_max_problems", "fused_rounds_max_blocks", "early_result", "early_run_ahead",
  * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "pair_chunk" (pairs per launch of hgs_calc_fitness_score_batch, 0 = 65535).  Results never depend on them (the tests
  * that force a code path check exactly that); A/B runs and those tests are the only callers — the library reads no tuning variable from the environment. */
