@@ -298,6 +298,39 @@ void launch_floor_ransac_decide(hipStream_t s, const int* counts, const double* 
                                 Progress prog);
 void launch_floor_inlier_flags(hipStream_t s, const float4* pts, int n, const FloorRansacState* st, double thresh, unsigned* keep);
 
+// floor detection of several clouds in one batch (hgs_detect_floor_batch): as in the batched prefilter the clouds lie concatenated in the work images,
+// cloud s in [off, off + n) of every array, the points a stage kept at the front of its slice.  One record per cloud in a device table; the kernels run
+// one grid row (blockIdx.y, the RANSAC kernels blockIdx.z / .x) per cloud.
+struct FloorSweep {
+  const float4* raw;                     // host: the resident input cloud
+  const float* intensity;
+  int off, n;                            // host: the cloud's slice
+  int n_clipped, n_filtered, n_inliers;  // k_flb_compact of the three stages: the points each kept
+  int pad;
+};
+// a cloud that entered RANSAC: its filtered points' slice of the filtered image and their number; job j owns FloorRansacState j
+struct FloorJob {
+  int off, n;
+};
+enum { kFlbClip = 0, kFlbNormal = 1, kFlbInliers = 2 };  // the stage whose count k_flb_compact writes
+void launch_flb_clip_flags(hipStream_t s, const FloorSweep* sweeps, int nsweeps, int max_n, FloorConsts c, float4* out, unsigned* keep);
+void launch_flb_compact(hipStream_t s, const float4* in, FloorSweep* sweeps, int nsweeps, int max_n, int stage, const unsigned* keep, const unsigned* slot, float4* out);
+// new resident clouds from slices of `in`: descs[c] (also what launch_bbox_count reads behind this) is written to *desc_outs[c], its points start at in[offs[c]]
+void launch_flb_to_cloud(hipStream_t s, const float4* in, const CloudDesc* descs, CloudDesc* const* desc_outs, float* const* intensities, const int* offs, int nclouds,
+                         int max_m);
+// k_knn_cov in its staging mode over `ncloud` indexed clouds (cloud c's covariances at raw_stage[(c * max_n + i) * 6]), then their normal flags at the
+// clipped points' original positions keep[keep_off[c] + o]
+void launch_flb_normals(hipStream_t s, const CloudDesc* descs, int ncloud, int max_n, int k, int qpw, int gather, double* raw_stage, const int* keep_off, FloorConsts c,
+                        unsigned* keep);
+void launch_flb_ransac_init(hipStream_t s, FloorRansacState* st, int njobs, int max_iterations, Progress prog);
+void launch_flb_ransac_planes(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, unsigned seed, int i0, int nh, int chunk, const FloorRansacState* st,
+                              double* planes /* [njobs][chunk][4] */, int* counts /* [njobs][chunk] */);
+void launch_flb_ransac_count(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, int max_n, double thresh, const double* planes, int nh, int chunk,
+                             const FloorRansacState* st, int* counts);
+void launch_flb_ransac_decide(hipStream_t s, const int* counts, const double* planes, const FloorJob* jobs, int njobs, int i0, int nh, int chunk, int max_iterations,
+                              double log_prob, FloorRansacState* st, Progress prog /* B = njobs */);
+void launch_flb_inlier_flags(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, int max_n, const FloorRansacState* st, double thresh, unsigned* keep);
+
 // stage-level test hooks
 void launch_gicp_debug_state(hipStream_t s, GicpState* st, const double* T12_dev);
 void launch_ndt_debug_state(hipStream_t s, NdtState* st, NdtAngles* ang, const double* p6_dev, NdtConsts c);

@@ -126,6 +126,8 @@ struct hgs_handle {
   int prefilter_fast = 1;  // hgs_prefilter: distance filter inside the voxel grid's kernels, RadiusOutlierRemoval on the voxel grid (0: the separate passes + search tree; A/B, tests)
   int upload_trace = 0;
   int floor_chunk = 64;    // hgs_detect_floor: hypotheses per RANSAC round (planes + count + decide); the result does not depend on it (tests)
+  int floor_batch_group = 0;  // hgs_detect_floor_batch: clouds per RANSAC launch group (0: what the work buffers allow); the result does not depend on it (tests)
+  int fb_clouds = 0, fb_ransac_clouds = 0, fb_rounds = 0, fb_readbacks = 0;  // the last hgs_detect_floor_batch (hgs_debug_floor_batch_stats)
   int early_run_ahead = 2;  // rounds the host keeps queued in front of a single registration that hands its result over early (the surplus drains behind the caller's back; 3 / 4 measured: no gain for the odometry source, config 2 0.837 -> 0.844 / 0.852 ms back to back: profiles/r06_ab16_early_run_ahead.log)
   int early_result = 1;    // a single registration in two-launch rounds hands its result over in host-mapped memory (run_batch; 0: result kernel + copy + synchronisation)
   PinnedBuffer h_early;                // the host-mapped record
@@ -1642,6 +1644,7 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
   else if (k == "upload_trace") h->upload_trace = value != 0 ? 1 : 0;
   else if (k == "prefilter_fast") h->prefilter_fast = value != 0 ? 1 : 0;
   else if (k == "floor_chunk") h->floor_chunk = std::max(1, std::min(kFloorMaxChunk, value));
+  else if (k == "floor_batch_group") h->floor_batch_group = std::max(0, value);                            // 0: what the work buffers allow
   else if (k == "pair_chunk") h->pair_chunk = std::max(0, std::min(65535, value));                         // 0: what one launch holds
   else {
     h->err = "hgs_debug_set_option: unknown option '" + k + "'";
@@ -3072,7 +3075,10 @@ int floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, con
       for (size_t i = 0; i < n; i++) keep_normal[i] = flags[i] ? 1 : 0;
     return HGS_OK;
   }
-  if (m == 0) return HGS_OK;
+  if (!floor_normals_defined(m)) {  // NaN normals: nothing passes (keep_normal and normals3 are already 0 / NaN)
+    w->n_filtered = 0;
+    return HGS_OK;
+  }
   // normal_filtering (:211-238): the clipped cloud gets a search index, k_knn_cov stages every point's fp64 neighbourhood covariance over its exact
   // min(normal_k, n_clipped) nearest neighbours (itself included; a list of k slots never fills in a smaller cloud), k_floor_normal_flags takes the
   // eigenvector of the smallest eigenvalue and tests it.  The viewpoint flip of pcl::NormalEstimation (:220) is irrelevant under |.| and not computed.
@@ -3133,6 +3139,27 @@ int floor_ransac_bufs(hgs_handle* h, int chunk, FloorRansacBufs* b) {
   return HGS_OK;
 }
 
+// the acceptance tests (:147-166) on a finished search and the number of its model's inliers: fills n_inliers, ransac_iterations, reason, detected, coeffs
+void floor_accept(const hgs_floor_params* p, const FloorConsts& c, const FloorRansacState& st, size_t n_in, hgs_floor_result* out) {
+  out->n_inliers = (uint32_t)n_in;
+  out->ransac_iterations = st.iterations;
+  float co[4] = {(float)st.plane[0], (float)st.plane[1], (float)st.plane[2], (float)st.plane[3]};
+  if (n_in < (size_t)p->floor_pts_thresh || st.best_i < 0) {  // :147
+    out->reason = HGS_FLOOR_TOO_FEW_INLIERS;
+    return;
+  }
+  // verticality (:152-161) against r = R^-1 e_z, then the upward flip (:164-166)
+  const double dot = (double)co[0] * c.nrx + (double)co[2] * c.nrz;
+  if (std::fabs(dot) < std::cos(p->floor_normal_thresh * M_PI / 180.0)) {
+    out->reason = HGS_FLOOR_NOT_VERTICAL;
+    return;
+  }
+  if (co[2] < 0.f)
+    for (float& v : co) v = -v;
+  for (int i = 0; i < 4; i++) out->coeffs[i] = co[i];
+  out->detected = 1, out->reason = HGS_FLOOR_DETECTED;
+}
+
 int detect_floor_locked(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out, FloorWork& w) {
   StageTimer tm(h, HGS_STAGE_PREFILTER);
   const FloorConsts c = floor_consts(p);
@@ -3172,25 +3199,238 @@ int detect_floor_locked(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params*
   FloorRansacState st;
   HGS_HIP(h, hipMemcpyAsync(&st, b.state, sizeof(st), hipMemcpyDeviceToHost, h->stream));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
-  out->n_inliers = (uint32_t)n_in;
-  out->ransac_iterations = st.iterations;
-  float co[4] = {(float)st.plane[0], (float)st.plane[1], (float)st.plane[2], (float)st.plane[3]};
-  if (n_in < (size_t)p->floor_pts_thresh || st.best_i < 0) {  // :147
-    out->reason = HGS_FLOOR_TOO_FEW_INLIERS;
-    return HGS_OK;
-  }
-  // verticality (:152-161) against r = R^-1 e_z, then the upward flip (:164-166)
-  const double dot = (double)co[0] * c.nrx + (double)co[2] * c.nrz;
-  if (std::fabs(dot) < std::cos(p->floor_normal_thresh * M_PI / 180.0)) {
-    out->reason = HGS_FLOOR_NOT_VERTICAL;
-    return HGS_OK;
-  }
-  if (co[2] < 0.f)
-    for (float& v : co) v = -v;
-  for (int i = 0; i < 4; i++) out->coeffs[i] = co[i];
-  out->detected = 1, out->reason = HGS_FLOOR_DETECTED;
-  if (inliers_out) HGS_TRY(cloud_from_device(h, w.spare, n_in, inliers_out));  // floor_points_pub (:168-177)
+  floor_accept(p, c, st, n_in, out);
+  if (out->detected && inliers_out) HGS_TRY(cloud_from_device(h, w.spare, n_in, inliers_out));  // floor_points_pub (:168-177)
   return HGS_OK;
+}
+
+// ---- several clouds in one batch (include/hgs_registration.h; the k_flb_* kernels of hgs_kernels.hip) ---------------------------------------
+// What the RANSAC rounds' counts and planes may take of h->misc (36 bytes per cloud and hypothesis of a chunk): more clouds run in groups, one after
+// the other.  The staged covariances of the normal filter (48 bytes per clipped point of the longest cloud of a launch, per cloud) likewise.
+constexpr size_t kFloorBatchWorkBytes = (size_t)64 << 20, kFloorBatchCovBytes = (size_t)256 << 20;
+
+// the table's counts (and whatever else the caller has queued for the host) in ONE copy and ONE synchronisation
+int floor_batch_readback(hgs_handle* h, size_t table_bytes) {
+  HGS_HIP(h, hipGetLastError());
+  HGS_HIP(h, hipMemcpyAsync(h->h_pf_table.p, h->pf_table.p, table_bytes, hipMemcpyDeviceToHost, h->stream));
+  HGS_HIP(h, hipStreamSynchronize(h->stream));
+  h->fb_readbacks++;
+  return HGS_OK;
+}
+
+// New resident clouds of counts[i] points from in[offs[i] ..): allocated here (out[i]; on a failure the caller frees what is there), made resident by ONE
+// k_flb_to_cloud and ONE k_bbox_count.
+int floor_batch_clouds(hgs_handle* h, const float4* in, const std::vector<int>& offs, const std::vector<size_t>& counts, hgs_cloud** out) {
+  const size_t K = offs.size();
+  if (K == 0) return HGS_OK;
+  size_t max_m = 0;
+  for (size_t i = 0; i < K; i++) {
+    HGS_TRY(cloud_alloc(h, counts[i], &out[i]));
+    max_m = std::max(max_m, counts[i]);
+  }
+  const size_t o_out = align_up(K * sizeof(CloudDesc), 16), o_int = o_out + K * sizeof(CloudDesc*), o_off = o_int + K * sizeof(float*), bytes = o_off + K * sizeof(int);
+  HGS_HIP(h, h->descs.reserve(bytes));
+  void* staged = nullptr;
+  int ring_slot = 0;
+  HGS_HIP(h, h->up.stage(bytes, &staged, &ring_slot));
+  char* hb = static_cast<char*>(staged);
+  for (size_t i = 0; i < K; i++) {
+    reinterpret_cast<CloudDesc*>(hb)[i] = resident_desc(out[i]);
+    reinterpret_cast<CloudDesc**>(hb + o_out)[i] = out[i]->dev_desc;
+    reinterpret_cast<float**>(hb + o_int)[i] = out[i]->intensity;
+    reinterpret_cast<int*>(hb + o_off)[i] = offs[i];
+  }
+  HGS_HIP(h, hipMemcpyAsync(h->descs.p, hb, bytes, hipMemcpyHostToDevice, h->stream));
+  HGS_HIP(h, h->up.commit(ring_slot, h->stream));
+  char* db = h->descs.as<char>();
+  launch_flb_to_cloud(h->stream, in, reinterpret_cast<const CloudDesc*>(db), reinterpret_cast<CloudDesc* const*>(db + o_out), reinterpret_cast<float* const*>(db + o_int),
+                      reinterpret_cast<const int*>(db + o_off), (int)K, (int)max_m);
+  launch_bbox_count(h->stream, reinterpret_cast<const CloudDesc*>(db), (int)K, (int)max_m);
+  HGS_HIP(h, hipGetLastError());
+  return HGS_OK;
+}
+
+// The normal filter of every clipped cloud: one launch of the new clouds, one index build, then k_knn_cov + the normal flags in one launch per set of
+// clouds that share k = min(normal_k, n_clipped) and the packet size the single call gives a cloud of that size (queries_per_wave) — the kernel takes one
+// of each per launch, and a cloud's sums are those of hgs_detect_floor only under the same two.  Sweeps of one sensor share both.
+int floor_batch_normals(hgs_handle* h, const hgs_floor_params* p, const FloorConsts& c, const std::vector<size_t>& off, const std::vector<size_t>& n_clipped,
+                        std::vector<hgs_cloud*>& clipped) {
+  struct Entry {
+    int sweep, k, qpw;
+  };
+  const int gather = h->knn_replay >= 0 ? h->knn_replay : 2;
+  std::vector<Entry> es;
+  for (size_t i = 0; i < n_clipped.size(); i++) {
+    const size_t m = n_clipped[i];
+    if (!floor_normals_defined(m)) continue;  // NaN normals: its flags stay 0 as the caller cleared them
+    const int k = (int)std::min<size_t>((size_t)p->normal_k, m);
+    int qpw = queries_per_wave(m, 32, h->knn_qpw_tiny, (size_t)h->knn_tiny_below);
+    if (qpw < 32 && (gather != 2 || k > 20)) qpw = 32;
+    es.push_back(Entry{(int)i, k, qpw});
+  }
+  const size_t K = es.size();
+  if (K == 0) return HGS_OK;
+  std::stable_sort(es.begin(), es.end(), [](const Entry& a, const Entry& b) { return a.k != b.k ? a.k > b.k : a.qpw < b.qpw; });
+  std::vector<int> offs(K);
+  std::vector<size_t> counts(K);
+  for (size_t j = 0; j < K; j++) offs[j] = (int)off[es[j].sweep], counts[j] = n_clipped[es[j].sweep];
+  clipped.assign(K, nullptr);
+  HGS_TRY(floor_batch_clouds(h, h->pf_b.as<float4>(), offs, counts, clipped.data()));
+  HGS_TRY(ensure_index(h, clipped));
+  // the launches: runs of equal (k, qpw), cut where the staged covariances would pass kFloorBatchCovBytes
+  struct Run {
+    size_t a, b, max_m;
+  };
+  std::vector<Run> runs;
+  size_t stage_doubles = 0;
+  for (size_t a = 0; a < K;) {
+    size_t b = a, max_m = 0;
+    while (b < K && es[b].k == es[a].k && es[b].qpw == es[a].qpw) {
+      const size_t mm = std::max(max_m, counts[b]);
+      if (b > a && (b - a + 1) * mm * 6 * sizeof(double) > kFloorBatchCovBytes) break;
+      max_m = mm, b++;
+    }
+    runs.push_back(Run{a, b, max_m});
+    stage_doubles = std::max(stage_doubles, (b - a) * max_m * 6);
+    a = b;
+  }
+  HGS_HIP(h, h->cov_raw.reserve(stage_doubles * sizeof(double)));
+  HGS_HIP(h, h->pf_small.reserve(256 + K * sizeof(int)));
+  int* d_keep_off = reinterpret_cast<int*>(h->pf_small.as<char>() + 256);
+  HGS_HIP(h, h->up.upload(d_keep_off, offs.data(), K * sizeof(int), h->stream));
+  const CloudDesc* d_descs = nullptr;
+  HGS_TRY(upload_descs(h, clipped, false, &d_descs, nullptr));
+  for (const Run& r : runs)
+    launch_flb_normals(h->stream, d_descs + r.a, (int)(r.b - r.a), (int)r.max_m, es[r.a].k, es[r.a].qpw, gather, h->cov_raw.as<double>(), d_keep_off + r.a, c,
+                       h->pf_keep.as<unsigned>());
+  HGS_HIP(h, hipGetLastError());
+  return HGS_OK;
+}
+
+int detect_floor_batch_impl(hgs_handle* h, hgs_cloud* const* clouds, size_t S, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out,
+                            hgs_cloud** inliers_out, std::vector<hgs_cloud*>& clipped) {
+  StageTimer tm(h, HGS_STAGE_PREFILTER);
+  const FloorConsts c = floor_consts(p);
+  std::vector<size_t> off(S + 1, 0);
+  size_t max_n = 0;
+  for (size_t i = 0; i < S; i++) off[i + 1] = off[i] + clouds[i]->n_input, max_n = std::max(max_n, clouds[i]->n_input);
+  const size_t total = off[S], cap = std::max<size_t>(total, 1), table_bytes = S * sizeof(FloorSweep);
+  HGS_HIP(h, h->pf_a.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_b.reserve(cap * sizeof(float4)));
+  HGS_HIP(h, h->pf_keep.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_slot.reserve(cap * sizeof(uint32_t)));
+  HGS_HIP(h, h->pf_table.reserve(table_bytes));
+  HGS_HIP(h, h->h_pf_table.reserve(table_bytes));
+  FloorSweep* d_sweeps = h->pf_table.as<FloorSweep>();
+  const FloorSweep* hs = h->h_pf_table.as<FloorSweep>();
+  float4* all = h->pf_a.as<float4>();
+  float4* clip = h->pf_b.as<float4>();
+  unsigned* keep = h->pf_keep.as<unsigned>();
+  unsigned* slot = h->pf_slot.as<unsigned>();
+  const int nS = (int)S, mx = (int)max_n;
+  std::vector<size_t> n_clipped(S, 0), n_filtered(S, 0);
+  float4 *filtered = clip, *spare = all;
+  if (total > 0) {
+    std::vector<FloorSweep> t(S);
+    for (size_t i = 0; i < S; i++) t[i] = FloorSweep{clouds[i]->desc.raw, clouds[i]->intensity, (int)off[i], (int)clouds[i]->n_input, 0, 0, 0, 0};
+    HGS_HIP(h, h->up.upload(d_sweeps, t.data(), table_bytes, h->stream));
+    // steps 1 and 2 of floor_filter, every cloud in its slice: ONE scan per compaction, the counts of all clouds in ONE read-back of the table
+    launch_flb_clip_flags(h->stream, d_sweeps, nS, mx, c, all, keep);
+    HGS_TRY(scan_u32(h, keep, slot, total));
+    launch_flb_compact(h->stream, all, d_sweeps, nS, mx, kFlbClip, keep, slot, clip);
+    HGS_TRY(floor_batch_readback(h, table_bytes));
+    for (size_t i = 0; i < S; i++) n_clipped[i] = n_filtered[i] = (size_t)std::max(0, hs[i].n_clipped);
+    if (p->use_normal_filtering && std::any_of(n_clipped.begin(), n_clipped.end(), [](size_t m) { return m > 0; })) {
+      HGS_HIP(h, hipMemsetAsync(keep, 0, total * sizeof(uint32_t), h->stream));
+      HGS_TRY(floor_batch_normals(h, p, c, off, n_clipped, clipped));
+      HGS_TRY(scan_u32(h, keep, slot, total));
+      launch_flb_compact(h->stream, clip, d_sweeps, nS, mx, kFlbNormal, keep, slot, all);
+      HGS_TRY(floor_batch_readback(h, table_bytes));
+      for (size_t i = 0; i < S; i++) n_filtered[i] = (size_t)std::max(0, hs[i].n_filtered);
+      filtered = all, spare = clip;
+    }
+  }
+  std::vector<int> offs(S);
+  for (size_t i = 0; i < S; i++) {
+    offs[i] = (int)off[i];
+    out[i].n_clipped = (uint32_t)n_clipped[i], out[i].n_filtered = (uint32_t)n_filtered[i];
+    out[i].reason = HGS_FLOOR_TOO_FEW_POINTS;  // :133 (an empty cloud / an empty clip range: not detected); the clouds that enter RANSAC get theirs below
+  }
+  if (filtered_out) HGS_TRY(floor_batch_clouds(h, filtered, offs, n_filtered, filtered_out));  // floor_filtered_pub (:127-130)
+  // RANSAC (:138-141): job j = the j-th cloud that passes the point-count test (:133).  One BatchLane per group of jobs with Progress::B = the group's
+  // jobs: each of them ticks once per round (k_flb_ransac_decide, one wave per job) and `finished` in the round that sets its `done`; the clouds that
+  // did not enter have no job, no wave and no tick.
+  std::vector<int> job_sweep;
+  std::vector<FloorJob> jobs;
+  size_t max_nf = 0;
+  for (size_t i = 0; i < S; i++)
+    if (n_filtered[i] > 0 && n_filtered[i] >= (size_t)p->floor_pts_thresh) {
+      job_sweep.push_back((int)i);
+      jobs.push_back(FloorJob{(int)off[i], (int)n_filtered[i]});
+      max_nf = std::max(max_nf, n_filtered[i]);
+    }
+  const size_t R = jobs.size();
+  h->fb_ransac_clouds = (int)R;
+  if (R == 0) return HGS_OK;
+  const int chunk = std::max(1, std::min(kFloorMaxChunk, h->floor_chunk));
+  const size_t per_job = (size_t)chunk * (sizeof(int) + 4 * sizeof(double));
+  size_t G = std::max<size_t>(1, kFloorBatchWorkBytes / per_job);
+  if (h->floor_batch_group > 0) G = std::min(G, (size_t)h->floor_batch_group);
+  G = std::min(G, R);
+  const size_t o_jobs = align_up(R * sizeof(FloorRansacState), 256), o_counts = o_jobs + align_up(R * sizeof(FloorJob), 256),
+               o_planes = o_counts + align_up(G * chunk * sizeof(int), 256);
+  HGS_HIP(h, h->misc.reserve(o_planes + G * chunk * 4 * sizeof(double)));
+  HGS_HIP(h, h->h_small.reserve(std::max<size_t>(256, R * sizeof(FloorRansacState))));
+  FloorRansacState* d_states = reinterpret_cast<FloorRansacState*>(h->misc.as<char>());
+  FloorJob* d_jobs = reinterpret_cast<FloorJob*>(h->misc.as<char>() + o_jobs);
+  int* d_counts = reinterpret_cast<int*>(h->misc.as<char>() + o_counts);
+  double* d_planes = reinterpret_cast<double*>(h->misc.as<char>() + o_planes);
+  HGS_HIP(h, h->up.upload(d_jobs, jobs.data(), R * sizeof(FloorJob), h->stream));
+  const long max_rounds = ((long)c.max_iterations + chunk - 1) / chunk;
+  for (size_t g0 = 0; g0 < R; g0 += G) {
+    const int ng = (int)std::min(G, R - g0);
+    if (g0 > 0) {  // make_progress resets the mirror: the rounds still queued for the group in front (they tick it) have to be through
+      HGS_HIP(h, hipStreamSynchronize(h->stream));
+      h->fb_readbacks++;
+    }
+    int group_max = 0;
+    for (int j = 0; j < ng; j++) group_max = std::max(group_max, jobs[g0 + j].n);
+    std::vector<BatchLane> lanes(1);
+    lanes[0].stream = h->stream, lanes[0].b0 = (int)g0, lanes[0].B = ng;
+    HGS_TRY(make_progress(h, 0, ng, &lanes[0].prog));
+    launch_flb_ransac_init(h->stream, d_states + g0, ng, c.max_iterations, lanes[0].prog);
+    drive_lanes(
+        lanes, max_rounds,
+        [&](BatchLane& L) {
+          const int i0 = (int)L.round * chunk;
+          const int nh = std::min(chunk, c.max_iterations - i0);
+          launch_flb_ransac_planes(h->stream, filtered, d_jobs + g0, ng, c.seed, i0, nh, chunk, d_states + g0, d_planes, d_counts);
+          launch_flb_ransac_count(h->stream, filtered, d_jobs + g0, ng, group_max, c.dist_thresh, d_planes, nh, chunk, d_states + g0, d_counts);
+          launch_flb_ransac_decide(h->stream, d_counts, d_planes, d_jobs + g0, ng, i0, nh, chunk, c.max_iterations, c.log_prob, d_states + g0, L.prog);
+          h->fb_rounds++;
+        },
+        [&](BatchLane&) {});
+  }
+  // every job's inliers from its own float-rounded model (:143-144), ONE scan, ONE compaction; counts and states in ONE read-back
+  HGS_HIP(h, hipMemsetAsync(keep, 0, total * sizeof(uint32_t), h->stream));
+  launch_flb_inlier_flags(h->stream, filtered, d_jobs, (int)R, (int)max_nf, d_states, c.dist_thresh, keep);
+  HGS_TRY(scan_u32(h, keep, slot, total));
+  launch_flb_compact(h->stream, filtered, d_sweeps, nS, mx, kFlbInliers, keep, slot, spare);
+  const FloorRansacState* st = h->h_small.as<FloorRansacState>();
+  HGS_HIP(h, hipMemcpyAsync(h->h_small.p, d_states, R * sizeof(FloorRansacState), hipMemcpyDeviceToHost, h->stream));
+  HGS_TRY(floor_batch_readback(h, table_bytes));
+  std::vector<int> in_offs, in_sweep;
+  std::vector<size_t> in_counts;
+  for (size_t j = 0; j < R; j++) {
+    const int i = job_sweep[j];
+    const size_t n_in = (size_t)std::max(0, hs[i].n_inliers);
+    floor_accept(p, c, st[j], n_in, &out[i]);
+    if (out[i].detected && inliers_out) in_offs.push_back((int)off[i]), in_counts.push_back(n_in), in_sweep.push_back(i);
+  }
+  std::vector<hgs_cloud*> in_clouds(in_offs.size(), nullptr);
+  const int rc = floor_batch_clouds(h, spare, in_offs, in_counts, in_clouds.data());  // floor_points_pub (:168-177)
+  for (size_t k = 0; k < in_clouds.size(); k++) inliers_out[in_sweep[k]] = in_clouds[k];  // (a failure: the caller frees them with the array)
+  return rc;
 }
 
 }  // namespace
@@ -3210,6 +3450,65 @@ extern "C" int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor
     if (inliers_out && *inliers_out) cloud_free(*inliers_out), *inliers_out = nullptr;
   }
   return rc;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_detect_floor_batch(hgs_handle* h, hgs_cloud* const* clouds, size_t n_clouds, const hgs_floor_params* p, hgs_floor_result* out,
+                                      hgs_cloud** filtered_out, hgs_cloud** inliers_out) try {
+  ApiLock lock(h);
+  for (size_t i = 0; i < n_clouds; i++) {
+    if (filtered_out) filtered_out[i] = nullptr;
+    if (inliers_out) inliers_out[i] = nullptr;
+  }
+  if (!h || !p || !floor_params_valid(p)) return HGS_ERR_INVALID_ARGUMENT;
+  h->fb_clouds = h->fb_ransac_clouds = h->fb_rounds = h->fb_readbacks = 0;
+  if (n_clouds == 0) return HGS_OK;
+  if (!clouds || !out) return HGS_ERR_INVALID_ARGUMENT;
+  if (n_clouds > HGS_FLOOR_BATCH_MAX_CLOUDS) {
+    h->err = "hgs_detect_floor_batch: more than " + std::to_string(HGS_FLOOR_BATCH_MAX_CLOUDS) + " clouds in one call";
+    return HGS_ERR_INVALID_ARGUMENT;
+  }
+  size_t total = 0;
+  for (size_t i = 0; i < n_clouds; i++) {
+    if (!clouds[i] || clouds[i]->owner != h) {
+      h->err = "hgs_detect_floor_batch: cloud " + std::to_string(i) + " is NULL or not a cloud of this engine";
+      return HGS_ERR_INVALID_ARGUMENT;
+    }
+    total += clouds[i]->n_input;
+  }
+  if (total > (size_t)1 << 30) {
+    h->err = "hgs_detect_floor_batch: more than 2^30 points in one call";
+    return HGS_ERR_INVALID_ARGUMENT;
+  }
+  HGS_TRY(set_device(h));
+  h->fb_clouds = (int)n_clouds;
+  std::memset(out, 0, n_clouds * sizeof(*out));
+  std::vector<hgs_cloud*> clipped;  // the clipped clouds with their indices (normal filter only)
+  int rc;
+  try {
+    rc = detect_floor_batch_impl(h, clouds, n_clouds, p, out, filtered_out, inliers_out, clipped);
+  } catch (...) {  // (a failed host allocation: the clouds made so far are freed below like after a HIP error)
+    rc = status_of_current_exception(h);
+  }
+  for (hgs_cloud* c : clipped) cloud_free(c);
+  if (rc != HGS_OK) {
+    if (filtered_out) free_clouds(filtered_out, n_clouds);
+    if (inliers_out) free_clouds(inliers_out, n_clouds);
+  }
+  return rc;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_debug_floor_batch_stats(hgs_handle* h, int32_t* clouds, int32_t* ransac_clouds, int32_t* ransac_rounds, int32_t* readbacks) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (clouds) *clouds = h->fb_clouds;
+  if (ransac_clouds) *ransac_clouds = h->fb_ransac_clouds;
+  if (ransac_rounds) *ransac_rounds = h->fb_rounds;
+  if (readbacks) *readbacks = h->fb_readbacks;
+  return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
 }

@@ -31,6 +31,11 @@ HGS_HD bool floor_clip_keep(const FloorConsts& c, float x, float y, float z) {
   return (zt + c.clip_lo >= 0.f) && !(zt + c.clip_hi >= 0.f);
 }
 
+// pcl::NormalEstimation gives a point with fewer than three neighbours (itself included) a NaN normal (pcl::computePointNormal), and the filter's test
+// on NaN fails: of a clipped cloud of fewer than three points the normal filter keeps nothing.  (Two points have a rank-1 covariance, whose smallest
+// eigenvector is any direction across the line between them.)
+HGS_HD bool floor_normals_defined(size_t n_clipped) { return n_clipped >= 3; }
+
 // unit eigenvector of the smallest eigenvalue of a neighbourhood covariance, and the normal filter's test |n . r| > cos(normal_filter_thresh)
 HGS_HD bool floor_normal_keep(const FloorConsts& c, const Sym3& cov, double* n3) {
   HGS_FP_STRICT

@@ -3393,11 +3393,10 @@ void launch_floor_ransac_init(hipStream_t s, FloorRansacState* st, int max_itera
   hipLaunchKernelGGL(k_floor_ransac_init, dim3(1), dim3(64), 0, s, st, max_iterations, prog);
 }
 
-// hypotheses i0 .. i0 + nh - 1: their planes (all zero: degenerate) and a zeroed count each
-__global__ __launch_bounds__(kBlock) void k_floor_ransac_planes(const float4* __restrict__ pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st,
-                                                                double* __restrict__ planes, int* __restrict__ counts) {
+// hypotheses i0 .. i0 + nh - 1 of one cloud: their planes (all zero: degenerate) and a zeroed count each (thread j of the row: hypothesis i0 + j)
+__device__ __forceinline__ void floor_planes_row(const float4* __restrict__ pts, int n, unsigned seed, int i0, int nh, double* __restrict__ planes, int* __restrict__ counts) {
   const int j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= nh || (st && st->done)) return;
+  if (j >= nh) return;
   counts[j] = 0;
   double pl[4] = {0.0, 0.0, 0.0, 0.0};
   if (n >= 3) {
@@ -3407,6 +3406,11 @@ __global__ __launch_bounds__(kBlock) void k_floor_ransac_planes(const float4* __
   }
   planes[4 * j] = pl[0], planes[4 * j + 1] = pl[1], planes[4 * j + 2] = pl[2], planes[4 * j + 3] = pl[3];
 }
+__global__ __launch_bounds__(kBlock) void k_floor_ransac_planes(const float4* __restrict__ pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st,
+                                                                double* __restrict__ planes, int* __restrict__ counts) {
+  if (st && st->done) return;
+  floor_planes_row(pts, n, seed, i0, nh, planes, counts);
+}
 void launch_floor_ransac_planes(hipStream_t s, const float4* pts, int n, unsigned seed, int i0, int nh, const FloorRansacState* st, double* planes, int* counts) {
   if (nh > 0) hipLaunchKernelGGL(k_floor_ransac_planes, dim3((nh + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pts, n, seed, i0, nh, st, planes, counts);
 }
@@ -3415,9 +3419,7 @@ void launch_floor_ransac_planes(hipStream_t s, const float4* pts, int n, unsigne
 // wave-uniform (scalar loads); one ballot per wave and hypothesis, the four waves' counts meet in LDS, one global atomic per block and hypothesis.
 // Algorithmic work per chunk: n * nh plane evaluations (7 fp64 operations each) against 16 n bytes per hypothesis group: VALU bound.
 constexpr int kFloorHypPerBlock = 16;
-__global__ __launch_bounds__(kBlock) void k_floor_ransac_count(const float4* __restrict__ pts, int n, double thresh, const double* __restrict__ planes, int nh,
-                                                               const FloorRansacState* st, int* __restrict__ counts) {
-  if (st && st->done) return;  // (grid-uniform: a finished search costs a launch, no work)
+__device__ __forceinline__ void floor_count_tile(const float4* __restrict__ pts, int n, double thresh, const double* __restrict__ planes, int nh, int* __restrict__ counts) {
   __shared__ int s_cnt[kFloorHypPerBlock];
   const int i = blockIdx.x * kBlock + threadIdx.x;
   const bool valid = i < n;
@@ -3436,6 +3438,11 @@ __global__ __launch_bounds__(kBlock) void k_floor_ransac_count(const float4* __r
   __syncthreads();
   if ((int)threadIdx.x < hn && s_cnt[threadIdx.x] != 0) atomicAdd(&counts[h0 + threadIdx.x], s_cnt[threadIdx.x]);
 }
+__global__ __launch_bounds__(kBlock) void k_floor_ransac_count(const float4* __restrict__ pts, int n, double thresh, const double* __restrict__ planes, int nh,
+                                                               const FloorRansacState* st, int* __restrict__ counts) {
+  if (st && st->done) return;  // (grid-uniform: a finished search costs a launch, no work)
+  floor_count_tile(pts, n, thresh, planes, nh, counts);
+}
 void launch_floor_ransac_count(hipStream_t s, const float4* pts, int n, double thresh, const double* planes, int nh, const FloorRansacState* st, int* counts) {
   if (n <= 0 || nh <= 0) return;
   hipLaunchKernelGGL(k_floor_ransac_count, dim3((n + kBlock - 1) / kBlock, (nh + kFloorHypPerBlock - 1) / kFloorHypPerBlock), dim3(kBlock), 0, s, pts, n, thresh,
@@ -3443,9 +3450,10 @@ void launch_floor_ransac_count(hipStream_t s, const float4* pts, int n, double t
 }
 
 // One wave replays the sequential rule over the chunk's counts in hypothesis order (64 counts per load, handed round with v_readlane; every lane
-// holds the same state): hypotheses from the stopping index on are ignored, and the chunk that reaches it sets `done`.
-__global__ __launch_bounds__(64) void k_floor_ransac_decide(const int* __restrict__ counts, const double* __restrict__ planes, int i0, int nh, int n, int max_iterations,
-                                                            double log_prob, FloorRansacState* st, Progress prog) {
+// holds the same state): hypotheses from the stopping index on are ignored, and the chunk that reaches it sets `done`.  Ticks the progress mirror
+// once, `finished` in the round that sets `done` and in no other.
+__device__ __forceinline__ void floor_decide_wave(const int* __restrict__ counts, const double* __restrict__ planes, int i0, int nh, int n, int max_iterations, double log_prob,
+                                                  FloorRansacState* st, Progress prog) {
   const int lane = (int)(threadIdx.x & 63);
   FloorRansacState s = *st;
   bool finished_now = false;
@@ -3472,21 +3480,172 @@ __global__ __launch_bounds__(64) void k_floor_ransac_decide(const int* __restric
   }
   if (lane == 0) progress_tick(prog, finished_now);
 }
+__global__ __launch_bounds__(64) void k_floor_ransac_decide(const int* __restrict__ counts, const double* __restrict__ planes, int i0, int nh, int n, int max_iterations,
+                                                            double log_prob, FloorRansacState* st, Progress prog) {
+  floor_decide_wave(counts, planes, i0, nh, n, max_iterations, log_prob, st, prog);
+}
 void launch_floor_ransac_decide(hipStream_t s, const int* counts, const double* planes, int i0, int nh, int n, int max_iterations, double log_prob, FloorRansacState* st,
                                 Progress prog) {
   hipLaunchKernelGGL(k_floor_ransac_decide, dim3(1), dim3(64), 0, s, counts, planes, i0, nh, n, max_iterations, log_prob, st, prog);
 }
 
 // the inliers of the chosen model — the best plane's coefficients rounded to float — as flags for the scan + k_pf_compact
+__device__ __forceinline__ unsigned floor_inlier_flag(const float4 p, const FloorRansacState* st, double thresh) {
+  const double pl[4] = {(double)(float)st->plane[0], (double)(float)st->plane[1], (double)(float)st->plane[2], (double)(float)st->plane[3]};
+  return (st->best_i >= 0 && floor_within(pl, (double)p.x, (double)p.y, (double)p.z, thresh)) ? 1u : 0u;
+}
 __global__ __launch_bounds__(kBlock) void k_floor_inlier_flags(const float4* __restrict__ pts, int n, const FloorRansacState* st, double thresh, unsigned* __restrict__ keep) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  const double pl[4] = {(double)(float)st->plane[0], (double)(float)st->plane[1], (double)(float)st->plane[2], (double)(float)st->plane[3]};
-  const float4 p = pts[i];
-  keep[i] = (st->best_i >= 0 && floor_within(pl, (double)p.x, (double)p.y, (double)p.z, thresh)) ? 1u : 0u;
+  keep[i] = floor_inlier_flag(pts[i], st, thresh);
 }
 void launch_floor_inlier_flags(hipStream_t s, const float4* pts, int n, const FloorRansacState* st, double thresh, unsigned* keep) {
   if (n > 0) hipLaunchKernelGGL(k_floor_inlier_flags, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pts, n, st, thresh, keep);
+}
+
+// ------------------------------------------------------------------------------------------------ floor detection, several clouds in one batch
+// hgs_detect_floor_batch: the k_floor_* sequence above over S clouds that lie concatenated in the work images (FloorSweep, hgs_device.h), one grid row per
+// cloud as in the k_pfb_* family.  A thread's index within its row is the point's (or the hypothesis') index within its OWN cloud, and every per-point and
+// per-hypothesis expression is the device function the single kernels call: cloud s comes out bit for bit as hgs_detect_floor gives it.  Shared between the
+// clouds: ONE exclusive scan per compaction, one index build and one k_knn_cov launch for the clipped clouds, and RANSAC rounds whose three launches carry
+// every cloud that is still searching.  Rows of clouds shorter than the longest one end at once.
+
+// k_floor_clip_flags per cloud, read through the table's resident descriptors.  Streaming: 20 bytes in, 20 out per point — HBM bound.
+__global__ __launch_bounds__(kBlock) void k_flb_clip_flags(const FloorSweep* __restrict__ sweeps, FloorConsts c, float4* __restrict__ out, unsigned* __restrict__ keep) {
+  const FloorSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= sw.n) return;
+  const float4 p = sw.raw[l];
+  out[sw.off + l] = make_float4(p.x, p.y, p.z, sw.intensity[l]);
+  keep[sw.off + l] = floor_clip_keep(c, p.x, p.y, p.z) ? 1u : 0u;
+}
+void launch_flb_clip_flags(hipStream_t s, const FloorSweep* sweeps, int nsweeps, int max_n, FloorConsts c, float4* out, unsigned* keep) {
+  if (max_n > 0) hipLaunchKernelGGL(k_flb_clip_flags, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, sweeps, c, out, keep);
+}
+
+// k_pf_compact per cloud (as k_pfb_compact): the kept points move to the front of the cloud's slice of `out`, the stage's count is taken at the slice's
+// end.  The flags cover the whole slice (0 behind the points of the stage in front).  HBM bound.
+__global__ __launch_bounds__(kBlock) void k_flb_compact(const float4* __restrict__ in, FloorSweep* __restrict__ sweeps, int stage, const unsigned* __restrict__ keep,
+                                                        const unsigned* __restrict__ slot, float4* __restrict__ out) {
+  FloorSweep& sw = sweeps[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x, n = sw.n, off = sw.off;
+  if (l >= n) return;
+  const int i = off + l;
+  const unsigned base = slot[off];
+  if (keep[i]) out[off + (int)(slot[i] - base)] = in[i];
+  if (l == n - 1) {
+    const int count = (int)(slot[i] + keep[i] - base);
+    if (stage == kFlbClip) sw.n_clipped = count;
+    else if (stage == kFlbNormal) sw.n_filtered = count;
+    else sw.n_inliers = count;
+  }
+}
+void launch_flb_compact(hipStream_t s, const float4* in, FloorSweep* sweeps, int nsweeps, int max_n, int stage, const unsigned* keep, const unsigned* slot, float4* out) {
+  if (max_n > 0) hipLaunchKernelGGL(k_flb_compact, dim3((max_n + kBlock - 1) / kBlock, nsweeps), dim3(kBlock), 0, s, in, sweeps, stage, keep, slot, out);
+}
+
+// k_pf_to_cloud for every new cloud of a list (descs[c].n_input = its count, read back by the host in front of the allocation)
+__global__ __launch_bounds__(kBlock) void k_flb_to_cloud(const float4* __restrict__ in, const CloudDesc* __restrict__ descs, CloudDesc* const* __restrict__ desc_outs,
+                                                         float* const* __restrict__ intensities, const int* __restrict__ offs) {
+  const CloudDesc d = descs[blockIdx.y];
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) {
+    meta_reset(d.meta);
+    *desc_outs[blockIdx.y] = d;
+  }
+  if (i >= d.n_input) return;
+  const float4 p = in[offs[blockIdx.y] + i];
+  const_cast<float4*>(d.raw)[i] = make_float4(p.x, p.y, p.z, __int_as_float(i));
+  intensities[blockIdx.y][i] = p.w;
+}
+void launch_flb_to_cloud(hipStream_t s, const float4* in, const CloudDesc* descs, CloudDesc* const* desc_outs, float* const* intensities, const int* offs, int nclouds,
+                         int max_m) {
+  if (nclouds > 0)
+    hipLaunchKernelGGL(k_flb_to_cloud, dim3(std::max(1, (max_m + kBlock - 1) / kBlock), nclouds), dim3(kBlock), 0, s, in, descs, desc_outs, intensities, offs);
+}
+
+// k_floor_normal_flags per clipped cloud: sorted point i writes the flag of its original position within the cloud's slice.  One 3x3 eigen-decomposition
+// per point from 48 staged bytes: VALU (fp64) bound.
+__global__ __launch_bounds__(kBlock) void k_flb_normal_flags(const CloudDesc* __restrict__ descs, const double* __restrict__ raw_cov, int raw_stride,
+                                                             const int* __restrict__ keep_off, FloorConsts c, unsigned* __restrict__ keep) {
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= d.meta->nvalid) return;
+  const int o = __float_as_int(d.pts[i].w);
+  if (o < 0 || o >= d.n_input) return;
+  const double* r = raw_cov + ((size_t)blockIdx.y * (size_t)raw_stride + (size_t)i) * 6;
+  double n3[3];
+  keep[keep_off[blockIdx.y] + o] = floor_normal_keep(c, Sym3{r[0], r[1], r[2], r[3], r[4], r[5]}, n3) ? 1u : 0u;
+}
+void launch_flb_normals(hipStream_t s, const CloudDesc* descs, int ncloud, int max_n, int k, int qpw, int gather, double* raw_stage, const int* keep_off, FloorConsts c,
+                        unsigned* keep) {
+  if (ncloud <= 0 || max_n <= 0) return;
+  launch_knn_cov_g<2>(s, descs, ncloud, max_n, k, qpw, HGS_REG_NONE, gather, raw_stage, max_n);
+  hipLaunchKernelGGL(k_flb_normal_flags, dim3((max_n + kBlock - 1) / kBlock, ncloud), dim3(kBlock), 0, s, descs, raw_stage, max_n, keep_off, c, keep);
+}
+
+// RANSAC: job j = a cloud that entered, FloorRansacState j its search; rows of the chunk's counts and planes per job.  A job whose search is done returns
+// at the top of planes and count (block-uniform); its decide wave still ticks once per round, so that the mirror's round count stays a multiple of B.
+__global__ void k_flb_ransac_init(FloorRansacState* st, int njobs, int max_iterations, Progress prog) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j == 0) prog.dev[0] = 0, prog.dev[1] = 0;
+  if (j < njobs) floor_ransac_init(st[j], max_iterations);
+}
+void launch_flb_ransac_init(hipStream_t s, FloorRansacState* st, int njobs, int max_iterations, Progress prog) {
+  hipLaunchKernelGGL(k_flb_ransac_init, dim3((std::max(njobs, 1) + 63) / 64), dim3(64), 0, s, st, njobs, max_iterations, prog);
+}
+
+__global__ __launch_bounds__(kBlock) void k_flb_ransac_planes(const float4* __restrict__ pts, const FloorJob* __restrict__ jobs, unsigned seed, int i0, int nh, int chunk,
+                                                              const FloorRansacState* __restrict__ st, double* __restrict__ planes, int* __restrict__ counts) {
+  const int b = blockIdx.y;
+  if (st[b].done) return;
+  floor_planes_row(pts + jobs[b].off, jobs[b].n, seed, i0, nh, planes + 4 * (size_t)b * chunk, counts + (size_t)b * chunk);
+}
+void launch_flb_ransac_planes(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, unsigned seed, int i0, int nh, int chunk, const FloorRansacState* st,
+                              double* planes, int* counts) {
+  if (nh > 0 && njobs > 0)
+    hipLaunchKernelGGL(k_flb_ransac_planes, dim3((nh + kBlock - 1) / kBlock, njobs), dim3(kBlock), 0, s, pts, jobs, seed, i0, nh, chunk, st, planes, counts);
+}
+
+// k_floor_ransac_count's tile with the job as blockIdx.z: the grid is sized by the largest filtered cloud, a block beyond its own cloud's tiles returns.
+// VALU (fp64) bound as the single kernel; S clouds put S times the blocks into one launch.
+__global__ __launch_bounds__(kBlock) void k_flb_ransac_count(const float4* __restrict__ pts, const FloorJob* __restrict__ jobs, double thresh, const double* __restrict__ planes,
+                                                             int nh, int chunk, const FloorRansacState* __restrict__ st, int* __restrict__ counts) {
+  const int b = blockIdx.z;
+  if (st[b].done) return;
+  const int n = jobs[b].n;
+  if ((int)(blockIdx.x * kBlock) >= n) return;
+  floor_count_tile(pts + jobs[b].off, n, thresh, planes + 4 * (size_t)b * chunk, nh, counts + (size_t)b * chunk);
+}
+void launch_flb_ransac_count(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, int max_n, double thresh, const double* planes, int nh, int chunk,
+                             const FloorRansacState* st, int* counts) {
+  if (max_n <= 0 || nh <= 0 || njobs <= 0) return;
+  hipLaunchKernelGGL(k_flb_ransac_count, dim3((max_n + kBlock - 1) / kBlock, (nh + kFloorHypPerBlock - 1) / kFloorHypPerBlock, njobs), dim3(kBlock), 0, s, pts, jobs,
+                     thresh, planes, nh, chunk, st, counts);
+}
+
+// one wave per job: every job ticks once per round, and `finished` in exactly one of them (Progress::B = njobs)
+__global__ __launch_bounds__(64) void k_flb_ransac_decide(const int* __restrict__ counts, const double* __restrict__ planes, const FloorJob* __restrict__ jobs, int i0, int nh,
+                                                          int chunk, int max_iterations, double log_prob, FloorRansacState* st, Progress prog) {
+  const int b = blockIdx.x;
+  floor_decide_wave(counts + (size_t)b * chunk, planes + 4 * (size_t)b * chunk, i0, nh, jobs[b].n, max_iterations, log_prob, st + b, prog);
+}
+void launch_flb_ransac_decide(hipStream_t s, const int* counts, const double* planes, const FloorJob* jobs, int njobs, int i0, int nh, int chunk, int max_iterations,
+                              double log_prob, FloorRansacState* st, Progress prog) {
+  if (njobs > 0) hipLaunchKernelGGL(k_flb_ransac_decide, dim3(njobs), dim3(64), 0, s, counts, planes, jobs, i0, nh, chunk, max_iterations, log_prob, st, prog);
+}
+
+// k_floor_inlier_flags per job, from that job's float-rounded model (the flags of clouds without a job stay as the host cleared them)
+__global__ __launch_bounds__(kBlock) void k_flb_inlier_flags(const float4* __restrict__ pts, const FloorJob* __restrict__ jobs, const FloorRansacState* __restrict__ st,
+                                                             double thresh, unsigned* __restrict__ keep) {
+  const FloorJob job = jobs[blockIdx.y];
+  const int l = blockIdx.x * kBlock + threadIdx.x;
+  if (l >= job.n) return;
+  keep[job.off + l] = floor_inlier_flag(pts[job.off + l], st + blockIdx.y, thresh);
+}
+void launch_flb_inlier_flags(hipStream_t s, const float4* pts, const FloorJob* jobs, int njobs, int max_n, const FloorRansacState* st, double thresh, unsigned* keep) {
+  if (njobs > 0 && max_n > 0)
+    hipLaunchKernelGGL(k_flb_inlier_flags, dim3((max_n + kBlock - 1) / kBlock, njobs), dim3(kBlock), 0, s, pts, jobs, st, thresh, keep);
 }
 
 }  // namespace hgs

@@ -53,12 +53,16 @@ class FloorDetector:
         self.last: L.HgsFloorResult | None = None
         self._filtered: DeviceCloud | None = None
         self._inliers: DeviceCloud | None = None
+        self.last_batch: list = []                  # the records of the last detect_batch
+        self._batch_filtered: list = []
+        self._batch_inliers: list = []
 
     def _drop_clouds(self):
-        for c in (self._filtered, self._inliers):
+        for c in (self._filtered, self._inliers, *self._batch_filtered, *self._batch_inliers):
             if c is not None:
                 c.close()
         self._filtered = self._inliers = None
+        self._batch_filtered, self._batch_inliers = [], []
 
     def detect(self, cloud) -> np.ndarray | None:
         e = self.engine
@@ -77,17 +81,53 @@ class FloorDetector:
         self._inliers = DeviceCloud._adopt(e, i) if i.value else None
         return np.array(res.coeffs, dtype=np.float32) if res.detected else None
 
+    def detect_batch(self, clouds) -> list:
+        """`detect` of several clouds in ONE device batch (hgs_detect_floor_batch): the sweeps of one sweep time, or of a replayed run, as
+        prefilter_batch returned them.  Returns one entry per cloud — float32[4] or None — each bit for bit what detect(clouds[i]) returns.  Every
+        entry of `clouds` is a DeviceCloud or a host array (uploaded for the call).  The records are kept as `last_batch`, the clouds behind
+        filtered_points(i) and floor_points(i)."""
+        e = self.engine
+        n = len(clouds)
+        self._drop_clouds()
+        uploaded = []
+        try:
+            dcs = []
+            for c in clouds:
+                if not isinstance(c, DeviceCloud):
+                    c = e.upload(c)
+                    uploaded.append(c)
+                dcs.append(c)
+            arr = (C.c_void_p * max(n, 1))(*[c._h.value for c in dcs])
+            res = (L.HgsFloorResult * max(n, 1))()
+            f, i = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+            e._check(L.lib().hgs_detect_floor_batch(e._h, arr, n, C.byref(self.params), res, f, i))
+        finally:
+            for c in uploaded:
+                c.close()
+        self.last_batch = [res[k] for k in range(n)]
+        self._batch_filtered = [DeviceCloud._adopt(e, C.c_void_p(f[k])) if f[k] else None for k in range(n)]
+        self._batch_inliers = [DeviceCloud._adopt(e, C.c_void_p(i[k])) if i[k] else None for k in range(n)]
+        return [np.array(r.coeffs, dtype=np.float32) if r.detected else None for r in self.last_batch]
+
+    def batch_stats(self) -> dict:
+        """hgs_debug_floor_batch_stats of the engine's last detect_batch: clouds, ransac_clouds, ransac_rounds, readbacks."""
+        v = [C.c_int32() for _ in range(4)]
+        self.engine._check(L.lib().hgs_debug_floor_batch_stats(self.engine._h, *[C.byref(x) for x in v]))
+        return dict(zip(("clouds", "ransac_clouds", "ransac_rounds", "readbacks"), (x.value for x in v)))
+
     @property
     def reason(self) -> str | None:
         return None if self.last is None else REASONS.get(self.last.reason, str(self.last.reason))
 
-    def filtered_points(self) -> np.ndarray | None:
-        """What floor_filtered_pub publishes (:127-130): the RANSAC input, downloaded on demand."""
-        return None if self._filtered is None else self._filtered.download()
+    def filtered_points(self, i: int | None = None) -> np.ndarray | None:
+        """What floor_filtered_pub publishes (:127-130): the RANSAC input, downloaded on demand (i: of cloud i of the last detect_batch)."""
+        c = self._filtered if i is None else self._batch_filtered[i]
+        return None if c is None else c.download()
 
-    def floor_points(self) -> np.ndarray | None:
-        """What floor_points_pub publishes (:168-177): the model's inliers (None when no floor was detected)."""
-        return None if self._inliers is None else self._inliers.download()
+    def floor_points(self, i: int | None = None) -> np.ndarray | None:
+        """What floor_points_pub publishes (:168-177): the model's inliers (None when no floor was detected; i: of cloud i of the last detect_batch)."""
+        c = self._inliers if i is None else self._batch_inliers[i]
+        return None if c is None else c.download()
 
     # ---- stage hooks (tests)
     def debug_filter(self, cloud: DeviceCloud):

@@ -120,15 +120,22 @@ class LockstepOdometry:
 
     prefilter_params (an hgs_prefilter_params): `matching` takes the RAW host sweeps and prefilters those of one sweep time in one prefilter_batch
     (hgs_prefilter_batch; base_link_transforms: one sensor -> base_link matrix, or None, per stream) instead of one prefilter call per stream; the
-    streams' own `downsample` then stays the identity.  Without it nothing changes."""
+    streams' own `downsample` then stays the identity.  Without it nothing changes.
 
-    def __init__(self, registration, n_streams: int, prefilter_params=None, base_link_transforms=None, **nodelet_params):
+    floor_detector (a FloorDetector on `registration`; needs prefilter_params): the sweeps prefiltered at one sweep time go through one detect_batch
+    (hgs_detect_floor_batch) — three of the reference's launch files run floor detection on /filtered_points next to the odometry.  The coefficients
+    are kept as `last_floors` (None for a stream without a sweep or without a floor).  The odoms do not depend on it; without it nothing changes."""
+
+    def __init__(self, registration, n_streams: int, prefilter_params=None, base_link_transforms=None, floor_detector=None, **nodelet_params):
         self.registration = registration
         self.streams = [ScanMatchingOdometry(registration, **nodelet_params) for _ in range(n_streams)]
         self.last_records = None
         self.prefilter_params = prefilter_params
         self.base_link_transforms = [None] * n_streams if base_link_transforms is None else list(base_link_transforms)
         assert len(self.base_link_transforms) == n_streams
+        assert floor_detector is None or (prefilter_params is not None and floor_detector.engine is registration)
+        self.floor_detector = floor_detector
+        self.last_floors = [None] * n_streams
 
     def _resident(self, cloud):
         return cloud if hasattr(cloud, "_h") else self.registration.upload(cloud)
@@ -143,6 +150,10 @@ class LockstepOdometry:
             clouds = list(clouds)
             for i, f in zip(have, filtered):
                 clouds[i] = f
+            if self.floor_detector is not None:
+                self.last_floors = [None] * len(self.streams)
+                for i, co in zip(have, self.floor_detector.detect_batch(filtered)):
+                    self.last_floors[i] = co
         odoms = [None] * len(self.streams)
         work = []
         for i, (st, cloud) in enumerate(zip(self.streams, clouds)):

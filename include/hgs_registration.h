@@ -384,8 +384,21 @@ int hgs_floor_params_default(hgs_floor_params* p);
 /* *filtered_out (NULL ok): the RANSAC input as a resident cloud, what floor_filtered_pub publishes (:127-130) — set whenever the call returns HGS_OK;
  * *inliers_out (NULL ok): the model's inliers in order, what floor_points_pub publishes (:168-177) — set when a floor was detected, else NULL.
  * Both belong to `h` and are the caller's to destroy.  HGS_ERR_INVALID_ARGUMENT: negative thresholds, normal_k outside 3..64, ransac_probability outside
- * (0, 1), non-finite parameters, a cloud of another handle.  The work is accounted under HGS_STAGE_PREFILTER. */
+ * (0, 1), non-finite parameters, a cloud of another handle.  The work is accounted under HGS_STAGE_PREFILTER.  With use_normal_filtering a clipped cloud of
+ * fewer than three points keeps nothing (pcl::NormalEstimation's normal of fewer than three neighbours is NaN): n_filtered 0, TOO_FEW_POINTS. */
 int hgs_detect_floor(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, hgs_floor_result* out, hgs_cloud** filtered_out, hgs_cloud** inliers_out);
+/* hgs_detect_floor of several resident clouds in ONE device batch (the sweeps hgs_prefilter_batch returned, already in base_link; one parameter set: one
+ * nodelet configuration).  out[i], filtered_out[i] and inliers_out[i] (either array may be NULL) are byte for byte what hgs_detect_floor(clouds[i]) gives on
+ * an engine of its own — ransac_iterations included —, and depend on clouds[i]'s points only; inliers_out[i] is NULL where no floor was detected.  A cloud
+ * may appear several times; a cloud of 0 points yields TOO_FEW_POINTS and an empty filtered cloud; n_clouds == 0 is HGS_OK.  The number of blocking
+ * read-backs does not grow with n_clouds.  The handle's target and source are neither read nor changed; the work is accounted under
+ * HGS_STAGE_PREFILTER.  HGS_ERR_INVALID_ARGUMENT, with nothing launched, `out` untouched and every entry of the two cloud arrays NULL: a NULL `clouds`
+ * or `out` with n_clouds > 0, a NULL entry, a cloud of another handle or an orphaned one, invalid parameters (as hgs_detect_floor), more than
+ * HGS_FLOOR_BATCH_MAX_CLOUDS clouds, more than 2^30 points in total.  A failure behind that (HIP, allocation) frees every cloud the call created, leaves both
+ * arrays all NULL and the engine usable.  Additive: HGS_ABI_VERSION is unchanged. */
+#define HGS_FLOOR_BATCH_MAX_CLOUDS 4096
+int hgs_detect_floor_batch(hgs_handle* h, hgs_cloud* const* clouds, size_t n_clouds, const hgs_floor_params* p, hgs_floor_result* out /* n_clouds */,
+                           hgs_cloud** filtered_out /* n_clouds entries, or NULL */, hgs_cloud** inliers_out /* n_clouds entries, or NULL */);
 
 /* ---- measurement ---------------------------------------------------------------------------------------- */
 enum hgs_stage {
@@ -430,6 +443,11 @@ int hgs_debug_floor_filter(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_para
 /* Floor detection, the RANSAC counting step (k_floor_ransac_planes + k_floor_ransac_count) with `cloud` taken as the filtered set: counts[j] and
  * coeffs4[4 j ..] (fp64 plane, zeros for a degenerate triple) of hypotheses i0 .. i0 + n - 1 under p->seed and p->ransac_distance_threshold. */
 int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_floor_params* p, uint32_t i0, uint32_t n, int32_t* counts, double* coeffs4);
+/* The engine's last hgs_detect_floor_batch: *clouds = the clouds it took, *ransac_clouds = how many of them entered RANSAC (n_filtered > 0 and >=
+ * floor_pts_thresh), *ransac_rounds = the rounds (planes + count + decide) it enqueued, *readbacks = the blocking host read-backs it made (stream
+ * synchronisations that wait for device results): one per compaction stage in front of RANSAC, one for the final counts and states, one between two
+ * launch groups ("floor_batch_group") — never one per cloud.  Any pointer may be NULL.  An additive debug symbol. */
+int hgs_debug_floor_batch_stats(hgs_handle* h, int32_t* clouds, int32_t* ransac_clouds, int32_t* ransac_rounds, int32_t* readbacks);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
 /* Voxels of the FAST_VGICP target's Gaussian voxel map (any order), built for the engine's resolution and correspondence_randomness if needed:
@@ -465,7 +483,8 @@ int hgs_debug_batch_order(hgs_handle* h, int32_t* order, int32_t cap, int32_t* n
 /* A measurement / test knob of one engine: "batch_lanes", "lane_start", "lane_order" (1: a FAST_GICP / FAST_VGICP batch of 8 or more problems that opens
  * several lanes runs the half whose guesses lie farthest from the target on highest-priority streams; records are handed back in the caller's order), "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
  * "seed_grid", "knn_replay", "ndt_resident", "ndt_chunk", "hilbert_levels", "nn_qpw", "nn_qpw16_below", "nn_qpw32_below", "fused_rounds", "fused_rounds_below", "fused_rounds_max_problems", "fused_rounds_max_blocks", "early_result", "early_run_ahead",
- * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "pair_chunk" (pairs per launch of hgs_calc_fitness_score_batch, 0 = 65535).  Results never depend on them (the tests
+ * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "floor_batch_group" (clouds per RANSAC launch group of
+ * hgs_detect_floor_batch, 0 = all that its work buffers allow), "pair_chunk" (pairs per launch of hgs_calc_fitness_score_batch, 0 = 65535).  Results never depend on them (the tests
  * that force a code path check exactly that); A/B runs and those tests are the only callers — the library reads no tuning variable from the environment. */
 int hgs_debug_set_option(hgs_handle* h, const char* key, int32_t value);
 
