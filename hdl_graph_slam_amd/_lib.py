@@ -114,7 +114,7 @@ EXPORTS = [
     "hgs_align", "hgs_transform_source", "hgs_fitness", "hgs_nn_target",
     "hgs_loop_match_batch", "hgs_loop_match_groups", "hgs_align_pairs", "hgs_select_best", "hgs_calc_fitness_score", "hgs_calc_fitness_score_batch",
     "hgs_comm_get_unique_id", "hgs_comm_init", "hgs_comm_finalize", "hgs_loop_match_batch_sharded",
-    "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_prefilter_framed", "hgs_prefilter_batch", "hgs_cloud_download", "hgs_map_cloud_generate",
+    "hgs_prefilter_params_default", "hgs_prefilter", "hgs_prefilter_deskewed", "hgs_prefilter_framed", "hgs_prefilter_batch", "hgs_debug_prefilter_batch_stats", "hgs_cloud_download", "hgs_map_cloud_generate",
     "hgs_floor_params_default", "hgs_detect_floor", "hgs_detect_floor_batch", "hgs_debug_floor_filter", "hgs_debug_floor_ransac_counts", "hgs_debug_floor_batch_stats",
     "hgs_profile_enable", "hgs_profile_read", "hgs_synchronize",
     "hgs_debug_target_covariances", "hgs_debug_gicp_linearize", "hgs_debug_icp_correspond", "hgs_debug_icp_step", "hgs_debug_ndt_cells", "hgs_debug_vgicp_voxels", "hgs_debug_cloud_seed_grid", "hgs_debug_ndt_derivatives", "hgs_debug_merge_shard_records", "hgs_debug_set_option",
@@ -168,6 +168,7 @@ def lib():
     L.hgs_prefilter_deskewed.argtypes = [vp, vp, sz, sz, C.POINTER(HgsPrefilterParams), vp, C.c_double, C.POINTER(vp)]
     L.hgs_prefilter_framed.argtypes = [vp, vp, sz, sz, C.POINTER(HgsPrefilterParams), vp, C.c_double, fp, C.POINTER(vp)]
     L.hgs_prefilter_batch.argtypes = [vp, C.POINTER(HgsPrefilterSweep), sz, C.POINTER(HgsPrefilterParams), C.POINTER(vp)]
+    L.hgs_debug_prefilter_batch_stats.argtypes = [vp] + [C.POINTER(C.c_int32)] * 5
     L.hgs_cloud_download.argtypes = [vp, vp, sz]
     L.hgs_map_cloud_generate.argtypes = [vp, C.POINTER(vp), vp, sz, C.c_double, C.POINTER(vp)]
     L.hgs_floor_params_default.argtypes = [C.POINTER(HgsFloorParams)]

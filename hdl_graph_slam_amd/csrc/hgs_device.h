@@ -285,6 +285,12 @@ void launch_pfb_grid_radius_flags(hipStream_t s, const float4* cen, const unsign
 // descs: the new clouds' resident descriptors (also what launch_bbox_count reads behind this), each written to *desc_outs[s]
 void launch_pfb_to_cloud(hipStream_t s, const float4* in, const PfSweep* sweeps, const CloudDesc* descs, CloudDesc* const* desc_outs, float* const* intensities, int nsweeps,
                          int max_m);
+// the outlier removals on a search tree over the `ncloud` indexed intermediate clouds of a batch, one grid row per cloud: cloud c's flags and mean
+// distances at keep_off[c] + the point's original index (keep and dist cleared by the caller), its sums at stats[2 c], stats[2 c + 1]
+void launch_pfb_radius_flags(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, float r2, int min_neighbors, unsigned* keep);
+void launch_pfb_mean_knn_dist(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, int mean_k, double* dist);
+void launch_pfb_statistical(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, const double* dist, double* stats /* [2 * ncloud] */,
+                            double stddev_mul, unsigned* keep);
 
 // floor detection (apps/floor_detection_nodelet.cpp:110-238; hgs_floor.h)
 void launch_floor_clip_flags(hipStream_t s, const float4* raw, const float* intensity, int n, FloorConsts c, float4* out /* {x, y, z, intensity} */, unsigned* keep);

@@ -128,6 +128,10 @@ struct hgs_handle {
   int floor_chunk = 64;    // hgs_detect_floor: hypotheses per RANSAC round (planes + count + decide); the result does not depend on it (tests)
   int floor_batch_group = 0;  // hgs_detect_floor_batch: clouds per RANSAC launch group (0: what the work buffers allow); the result does not depend on it (tests)
   int fb_clouds = 0, fb_ransac_clouds = 0, fb_rounds = 0, fb_readbacks = 0;  // the last hgs_detect_floor_batch (hgs_debug_floor_batch_stats)
+  int prefilter_batch_tree = 1;  // hgs_prefilter_batch: the outlier removals on a search tree run behind the batched front (0: sweep after sweep, prefilter_each; A/B, tests)
+  struct PfBatchStats {
+    int sweeps = 0, batched = 0, readbacks = 0, index_builds = 0, tree_launches = 0;
+  } pb;  // the last hgs_prefilter_batch (hgs_debug_prefilter_batch_stats)
   int early_run_ahead = 2;  // rounds the host keeps queued in front of a single registration that hands its result over early (the surplus drains behind the caller's back; 3 / 4 measured: no gain for the odometry source, config 2 0.837 -> 0.844 / 0.852 ms back to back: profiles/r06_ab16_early_run_ahead.log)
   int early_result = 1;    // a single registration in two-launch rounds hands its result over in host-mapped memory (run_batch; 0: result kernel + copy + synchronisation)
   PinnedBuffer h_early;                // the host-mapped record
@@ -1643,6 +1647,7 @@ int hgs_debug_set_option(hgs_handle* h, const char* key, int value) try {
   else if (k == "nn_qpw32_below") h->nn_qpw32_below = std::max(0, value);
   else if (k == "upload_trace") h->upload_trace = value != 0 ? 1 : 0;
   else if (k == "prefilter_fast") h->prefilter_fast = value != 0 ? 1 : 0;
+  else if (k == "prefilter_batch_tree") h->prefilter_batch_tree = value != 0 ? 1 : 0;
   else if (k == "floor_chunk") h->floor_chunk = std::max(1, std::min(kFloorMaxChunk, value));
   else if (k == "floor_batch_group") h->floor_batch_group = std::max(0, value);                            // 0: what the work buffers allow
   else if (k == "pair_chunk") h->pair_chunk = std::max(0, std::min(65535, value));                         // 0: what one launch holds
@@ -2528,7 +2533,7 @@ static int prefilter_sweep_args(hgs_handle* h, const void* pts, size_t n, size_t
 // the one sequence behind hgs_prefilter, hgs_prefilter_deskewed and hgs_prefilter_framed.  imu_angular_velocity null: no deskewing; sensor_to_base null:
 // no transform (then the launches and their arguments are those of the two older entry points)
 static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t stride_bytes, const hgs_prefilter_params* p, const double* imu_angular_velocity,
-                          double scan_period, const float* sensor_to_base, hgs_cloud** out) {
+                          double scan_period, const float* sensor_to_base, hgs_cloud** out, hgs_handle::PfBatchStats* stats = nullptr) {
   ApiLock lock(h);
   if (!h || !p || !out || !prefilter_params_ok(p)) return HGS_ERR_INVALID_ARGUMENT;
   PfSweepArgs args;
@@ -2622,6 +2627,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
   // the point count (pf_small[0]) and the voxel grid's overflow flag (d_meta[12] = pf_small[28]) in ONE copy
   HGS_HIP(h, hipMemcpyAsync(hs, d_count, 32 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
+  if (stats) stats->readbacks++;
   size_t m = (size_t)std::max(0, hs[0]);
   if (n > 0 && p->downsample_method == HGS_DOWNSAMPLE_VOXELGRID && hs[16 + 12]) {
     h->err = "prefilter: voxel grid too fine for this cloud (index overflow; pcl::VoxelGrid refuses it too)";
@@ -2632,6 +2638,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
   if (m > 0 && p->outlier_removal_method != HGS_OUTLIER_NONE && !grid_radius) {
     std::vector<hgs_cloud*> one{c};
     int rc = ensure_index(h, one);
+    if (stats) stats->index_builds++;
     if (rc == HGS_OK) {
       hipError_t e = hipMemsetAsync(h->pf_keep.p, 0, m * sizeof(uint32_t), h->stream);  // non-finite points are dropped: only valid points get a flag
       if (e != hipSuccess) rc = HGS_ERR_HIP;
@@ -2655,6 +2662,7 @@ static int prefilter_impl(hgs_handle* h, const void* pts, size_t n, size_t strid
       hipError_t e = hipMemcpyAsync(hs, d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
       if (e != hipSuccess) rc = HGS_ERR_HIP;
+      if (stats) stats->readbacks++;
     }
     cloud_free(c);
     c = nullptr;
@@ -2691,15 +2699,31 @@ extern "C" int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, si
 // ---- several sweeps in one batch (include/hgs_registration.h; the k_pfb_* kernels of hgs_kernels.hip) -------------------------------------------------
 namespace {
 
-// Which parameter sets the batch runs itself: no downsampling or pcl::VoxelGrid, behind it no outlier removal or RadiusOutlierRemoval on the voxel grid
-// (what prefilter_impl calls grid_radius).  Everything else — ApproximateVoxelGrid's sequential history table, the outlier removals that need a search
-// tree per cloud — runs sweep after sweep through prefilter_impl inside the call.
-bool prefilter_batched(const hgs_handle* h, const hgs_prefilter_params* p) {
-  if (p->downsample_method == HGS_DOWNSAMPLE_APPROX_VOXELGRID) return false;
-  if (p->outlier_removal_method == HGS_OUTLIER_NONE) return true;
+// RadiusOutlierRemoval on the voxel grid (what prefilter_impl calls grid_radius): no search tree
+bool prefilter_grid_radius(const hgs_handle* h, const hgs_prefilter_params* p) {
   return p->downsample_method == HGS_DOWNSAMPLE_VOXELGRID && h->prefilter_fast && p->outlier_removal_method == HGS_OUTLIER_RADIUS &&
          p->radius_radius / p->downsample_resolution <= 4.0;
 }
+
+// Which parameter sets the batch runs itself: no downsampling or pcl::VoxelGrid, behind it any outlier removal — none, RadiusOutlierRemoval on the voxel
+// grid, or one on a search tree per cloud (STATISTICAL and the other RADIUS shapes: the tail of prefilter_batch_impl; "prefilter_batch_tree" = 0 sends
+// those sweep after sweep through prefilter_impl as ApproximateVoxelGrid's sequential history table always goes).
+bool prefilter_batched(const hgs_handle* h, const hgs_prefilter_params* p) {
+  if (p->downsample_method == HGS_DOWNSAMPLE_APPROX_VOXELGRID) return false;
+  return p->outlier_removal_method == HGS_OUTLIER_NONE || prefilter_grid_radius(h, p) || h->prefilter_batch_tree;
+}
+
+int floor_batch_clouds(hgs_handle* h, const float4* in, const std::vector<int>& offs, const std::vector<size_t>& counts, hgs_cloud** out);  // (below)
+
+// clouds that live for the length of one call: freed on every way out of it
+struct ScratchClouds {
+  std::vector<hgs_cloud*> list;
+  void release() {
+    for (hgs_cloud* c : list) cloud_free(c);
+    list.clear();
+  }
+  ~ScratchClouds() { release(); }
+};
 
 void free_clouds(hgs_cloud** out, size_t n) {
   for (size_t i = 0; i < n; i++) {
@@ -2712,7 +2736,7 @@ void free_clouds(hgs_cloud** out, size_t n) {
 int prefilter_each(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_t S, const hgs_prefilter_params* p, hgs_cloud** out) {
   for (size_t i = 0; i < S; i++) {
     const hgs_prefilter_sweep& w = sweeps[i];
-    const int rc = prefilter_impl(h, w.pts, w.n, w.stride_bytes, p, w.imu_angular_velocity, w.scan_period, w.sensor_to_base, &out[i]);
+    const int rc = prefilter_impl(h, w.pts, w.n, w.stride_bytes, p, w.imu_angular_velocity, w.scan_period, w.sensor_to_base, &out[i], &h->pb);
     if (rc != HGS_OK) {
       h->err = "sweep " + std::to_string(i) + ": " + h->err;
       free_clouds(out, S);
@@ -2769,6 +2793,7 @@ int prefilter_batch_impl(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_
   launch_pfb_load(h->stream, h->staging.as<float4>(), d_sweeps, nS, mx, cur);
   const bool voxelgrid = total > 0 && p->downsample_method == HGS_DOWNSAMPLE_VOXELGRID;
   const int inline_dist = (voxelgrid && p->use_distance_filter && h->prefilter_fast) ? 1 : 0;
+  const bool grid_radius = voxelgrid && prefilter_grid_radius(h, p);
   if (total > 0 && p->use_distance_filter && !inline_dist) {
     launch_pfb_distance_flags(h->stream, cur, d_sweeps, nS, mx, p->distance_near_thresh, p->distance_far_thresh, keep);
     HGS_TRY(scan_u32(h, keep, slot, total));
@@ -2787,7 +2812,6 @@ int prefilter_batch_impl(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_
     HGS_TRY(sort_pairs(h, total, 0, 32 + ordinal_bits));  // stable: every sweep keeps its slice, in the order its own sort over bits 0..31 gives
     launch_pfb_voxel_heads(h->stream, h->sort_keys[1].as<unsigned long long>(), d_sweeps, nS, mx, keep);
     HGS_TRY(scan_u32(h, keep, slot, total));
-    const bool grid_radius = p->outlier_removal_method == HGS_OUTLIER_RADIUS;  // (prefilter_batched: on the voxel grid, or not here at all)
     unsigned* ukeys = nullptr;
     if (grid_radius) {
       HGS_HIP(h, h->pf_ukeys.reserve(total * sizeof(uint32_t)));
@@ -2808,12 +2832,56 @@ int prefilter_batch_impl(hgs_handle* h, const hgs_prefilter_sweep* sweeps, size_
   const PfSweep* hs = h->h_pf_table.as<PfSweep>();
   HGS_HIP(h, hipMemcpyAsync(h->h_pf_table.p, d_sweeps, table_bytes, hipMemcpyDeviceToHost, h->stream));
   HGS_HIP(h, hipStreamSynchronize(h->stream));
+  h->pb.readbacks++;
   if (voxelgrid)
     for (size_t i = 0; i < S; i++)
       if (sweeps[i].n > 0 && hs[i].meta[12]) {
         h->err = "sweep " + std::to_string(i) + ": prefilter: voxel grid too fine for this cloud (index overflow; pcl::VoxelGrid refuses it too)";
         return HGS_ERR_INVALID_ARGUMENT;
       }
+  // The outlier removals on a search tree (prefilter_impl's second half for every sweep at once): the K sweeps that still have points become resident
+  // clouds out of their slices in one launch, get their indices in ONE build and their flags in ONE launch over the K descriptors, one grid row per cloud;
+  // a flag lands at the point's position in its sweep's slice, so that ONE scan and k_pfb_compact finish every sweep.  Then the table again: the final counts.
+  if (p->outlier_removal_method != HGS_OUTLIER_NONE && !grid_radius) {
+    std::vector<int> offs;
+    std::vector<size_t> counts;
+    size_t max_mid = 0;
+    for (size_t i = 0; i < S; i++)
+      if (hs[i].count > 0) offs.push_back((int)off[i]), counts.push_back((size_t)hs[i].count), max_mid = std::max(max_mid, (size_t)hs[i].count);
+    const size_t K = offs.size();
+    if (K > 0) {
+      ScratchClouds mid;
+      mid.list.assign(K, nullptr);
+      HGS_TRY(floor_batch_clouds(h, cur, offs, counts, mid.list.data()));
+      h->pb.index_builds++;
+      HGS_TRY(ensure_index(h, mid.list));
+      HGS_HIP(h, hipMemsetAsync(keep, 0, total * sizeof(uint32_t), h->stream));  // non-finite points are dropped: only valid points get a flag
+      const size_t o_stats = 256 + align_up(K * sizeof(int), 16);
+      HGS_HIP(h, h->pf_small.reserve(o_stats + 2 * K * sizeof(double)));
+      int* d_keep_off = reinterpret_cast<int*>(h->pf_small.as<char>() + 256);
+      double* d_stats = reinterpret_cast<double*>(h->pf_small.as<char>() + o_stats);
+      HGS_HIP(h, h->up.upload(d_keep_off, offs.data(), K * sizeof(int), h->stream));
+      const CloudDesc* d_descs = nullptr;
+      HGS_TRY(upload_descs(h, mid.list, false, &d_descs, nullptr));
+      h->pb.tree_launches++;
+      if (p->outlier_removal_method == HGS_OUTLIER_RADIUS) {
+        launch_pfb_radius_flags(h->stream, d_descs, (int)K, (int)max_mid, d_keep_off, (float)(p->radius_radius * p->radius_radius), p->radius_min_neighbors, keep);
+      } else {
+        HGS_HIP(h, h->pf_dist.reserve(total * sizeof(double)));
+        HGS_HIP(h, hipMemsetAsync(h->pf_dist.p, 0, total * sizeof(double), h->stream));
+        launch_pfb_mean_knn_dist(h->stream, d_descs, (int)K, (int)max_mid, d_keep_off, p->statistical_mean_k, h->pf_dist.as<double>());
+        launch_pfb_statistical(h->stream, d_descs, (int)K, (int)max_mid, d_keep_off, h->pf_dist.as<double>(), d_stats, p->statistical_stddev, keep);
+      }
+      HGS_TRY(scan_u32(h, keep, slot, total));
+      launch_pfb_compact(h->stream, cur, d_sweeps, nS, mx, keep, slot, other);
+      std::swap(cur, other);
+      HGS_HIP(h, hipGetLastError());
+      HGS_HIP(h, hipMemcpyAsync(h->h_pf_table.p, d_sweeps, table_bytes, hipMemcpyDeviceToHost, h->stream));
+      HGS_HIP(h, hipStreamSynchronize(h->stream));
+      h->pb.readbacks++;
+      // (nothing queued reads the intermediate clouds any more: their blocks go back to the pool in front of the allocations below)
+    }
+  }
   size_t max_m = 0;
   for (size_t i = 0; i < S; i++) {
     const size_t m = (size_t)std::max(0, hs[i].count);
@@ -2872,10 +2940,31 @@ extern "C" int hgs_prefilter_batch(hgs_handle* h, const hgs_prefilter_sweep* swe
   }
   HGS_TRY(set_device(h));
   for (size_t i = 0; i < n_sweeps; i++) out[i] = nullptr;
+  h->pb = hgs_handle::PfBatchStats{};
+  h->pb.sweeps = (int)n_sweeps;
   if (n_sweeps == 1 || !prefilter_batched(h, p)) return prefilter_each(h, sweeps, n_sweeps, p, out);
-  const int rc = prefilter_batch_impl(h, sweeps, n_sweeps, args, p, out);
+  h->pb.batched = 1;
+  int rc;
+  try {
+    rc = prefilter_batch_impl(h, sweeps, n_sweeps, args, p, out);
+  } catch (...) {  // (a failed host allocation: the clouds made so far are freed below like after a HIP error)
+    rc = status_of_current_exception(h);
+  }
   if (rc != HGS_OK) free_clouds(out, n_sweeps);
   return rc;
+} catch (...) {
+  return status_of_current_exception(h);
+}
+
+extern "C" int hgs_debug_prefilter_batch_stats(hgs_handle* h, int32_t* sweeps, int32_t* batched, int32_t* readbacks, int32_t* index_builds, int32_t* tree_launches) try {
+  ApiLock lock(h);
+  if (!h) return HGS_ERR_INVALID_ARGUMENT;
+  if (sweeps) *sweeps = h->pb.sweeps;
+  if (batched) *batched = h->pb.batched;
+  if (readbacks) *readbacks = h->pb.readbacks;
+  if (index_builds) *index_builds = h->pb.index_builds;
+  if (tree_launches) *tree_launches = h->pb.tree_launches;
+  return HGS_OK;
 } catch (...) {
   return status_of_current_exception(h);
 }

@@ -3342,6 +3342,116 @@ void launch_pfb_to_cloud(hipStream_t s, const float4* in, const PfSweep* sweeps,
   hipLaunchKernelGGL(k_pfb_to_cloud, dim3(std::max(1, (max_m + kBlock - 1) / kBlock), nsweeps), dim3(kBlock), 0, s, in, sweeps, descs, desc_outs, intensities);
 }
 
+// The outlier removals that need a search tree (k_pf_radius_flags, k_pf_mean_knn_dist, k_pf_dist_stats, k_pf_statistical_flags) over the K intermediate
+// clouds of a batch: one grid row per cloud (blockIdx.y), the cloud read from the launch's descriptor array (problem_cloud), its flags and distances at
+// keep_off[y] + the point's ORIGINAL index — the start of the cloud's sweep's slice of the work buffers.  Per point the walk, the lane and the expressions
+// are the single kernels': a row walks its own tree only, and its results are bit for bit those of the single launch on that cloud.  A block past its
+// row's nvalid returns before its walk (rows of clouds shorter than the longest one).  Issue-bound packet walks like their single twins.
+__global__ __launch_bounds__(kBlock) void k_pfb_radius_flags(const CloudDesc* __restrict__ descs, const int* __restrict__ keep_off, float r2, int min_neighbors,
+                                                             unsigned* __restrict__ keep) {
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
+  const int n = d.meta->nvalid;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (blockIdx.x * kBlock >= n) return;
+  const bool active = i < n;
+  BvhView tv;
+  tv.nodes = d.nodes, tv.pts = d.pts, tv.lpts = d.lpts, tv.P = d.P, tv.n = n;
+  __shared__ __attribute__((aligned(128))) float walk_slots[kBlock / 64][32];
+  const float4 qp = active ? d.pts[i] : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.f);
+  PacketWalk<RadiusCountLane> w[1];
+  w[0].lane.r2 = active ? r2 : -1.f, w[0].lane.cnt = 0, w[0].lane.need = min_neighbors + 1;
+  w[0].start(tv, F3{qp.x, qp.y, qp.z}, 31 - __clz(tv.P));
+  wave_walk_multi<RadiusCountLane, 1>(tv, w, walk_slots[threadIdx.x >> 6]);
+  const int orig = __float_as_int(qp.w);
+  if (active && orig >= 0 && orig < d.n_input) keep[keep_off[blockIdx.y] + orig] = w[0].lane.cnt > min_neighbors ? 1u : 0u;
+}
+void launch_pfb_radius_flags(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, float r2, int min_neighbors, unsigned* keep) {
+  if (ncloud > 0 && max_m > 0)
+    hipLaunchKernelGGL(k_pfb_radius_flags, dim3((max_m + kBlock - 1) / kBlock, ncloud), dim3(kBlock), 0, s, descs, keep_off, r2, min_neighbors, keep);
+}
+
+template <int KMAX>
+__global__ __launch_bounds__(kBlock) void k_pfb_mean_knn_dist(const CloudDesc* __restrict__ descs, const int* __restrict__ keep_off, int mean_k, double* __restrict__ dist) {
+  HGS_FP_STRICT
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
+  const int n = d.meta->nvalid;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (blockIdx.x * kBlock >= n) return;
+  const bool active = i < n;
+  BvhView tv;
+  tv.nodes = d.nodes, tv.pts = d.pts, tv.lpts = d.lpts, tv.P = d.P, tv.n = n;
+  __shared__ __attribute__((aligned(128))) float walk_slots[kBlock / 64][32];
+  const float4 qp = active ? d.pts[i] : make_float4(FLT_MAX, FLT_MAX, FLT_MAX, 0.f);
+  const int live = mean_k + 1 < KMAX ? mean_k + 1 : KMAX;
+  PacketWalk<KnnRadiusLane<KMAX>> w[1];
+  w[0].lane.init(live, active);
+  w[0].start(tv, F3{qp.x, qp.y, qp.z}, 31 - __clz(tv.P));
+  wave_walk_multi<KnnRadiusLane<KMAX>, 1>(tv, w, walk_slots[threadIdx.x >> 6]);
+  if (!active) return;
+  double sum = 0.0;
+  int found = 0;
+#pragma unroll
+  for (int j = KMAX - live; j < KMAX; j++) {
+    const float dd = w[0].lane.d[j];
+    if (dd < FLT_MAX) {
+      if (found > 0) sum += sqrt((double)dd);  // ascending; the first (the point itself) is dropped
+      found++;
+    }
+  }
+  const int orig = __float_as_int(qp.w);
+  if (orig >= 0 && orig < d.n_input) dist[keep_off[blockIdx.y] + orig] = found > 1 ? sum / (double)mean_k : 0.0;
+}
+void launch_pfb_mean_knn_dist(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, int mean_k, double* dist) {
+  if (ncloud <= 0 || max_m <= 0) return;
+  const dim3 grid((max_m + kBlock - 1) / kBlock, ncloud), block(kBlock);
+  if (mean_k + 1 <= 16) hipLaunchKernelGGL(k_pfb_mean_knn_dist<16>, grid, block, 0, s, descs, keep_off, mean_k, dist);
+  else if (mean_k + 1 <= 32) hipLaunchKernelGGL(k_pfb_mean_knn_dist<32>, grid, block, 0, s, descs, keep_off, mean_k, dist);
+  else hipLaunchKernelGGL(k_pfb_mean_knn_dist<64>, grid, block, 0, s, descs, keep_off, mean_k < 63 ? mean_k : 63, dist);  // (as launch_pf_mean_knn_dist)
+}
+// k_pf_dist_stats, one block per cloud over the n_input entries of ITS slice of dist[]: the per-thread strided sums and the tree over the block run in the
+// single kernel's order, which depends on the cloud's own count alone — stats[2 y] and stats[2 y + 1] are bitwise the single call's sums
+__global__ __launch_bounds__(kBlock) void k_pfb_dist_stats(const CloudDesc* __restrict__ descs, const int* __restrict__ keep_off, const double* __restrict__ dist_all,
+                                                           double* __restrict__ stats) {
+  __shared__ double s1[kBlock], s2[kBlock];
+  const int n = descs[blockIdx.x].n_input;
+  const double* __restrict__ dist = dist_all + keep_off[blockIdx.x];
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) {
+    const double v = dist[i];
+    a += v, b += v * v;
+  }
+  s1[threadIdx.x] = a, s2[threadIdx.x] = b;
+  __syncthreads();
+  for (int off = kBlock / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s1[threadIdx.x] += s1[threadIdx.x + off], s2[threadIdx.x] += s2[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) stats[2 * blockIdx.x] = s1[0], stats[2 * blockIdx.x + 1] = s2[0];
+}
+__global__ __launch_bounds__(kBlock) void k_pfb_statistical_flags(const CloudDesc* __restrict__ descs, const int* __restrict__ keep_off, const double* __restrict__ dist_all,
+                                                                  const double* __restrict__ stats_all, double stddev_mul, unsigned* __restrict__ keep) {
+  HGS_FP_STRICT
+  const CloudDesc d = problem_cloud(descs, blockIdx.y);
+  const int n = d.meta->nvalid;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int orig = __float_as_int(d.pts[i].w);
+  if (orig < 0 || orig >= d.n_input) return;
+  const int off = keep_off[blockIdx.y];
+  const double* __restrict__ stats = stats_all + 2 * blockIdx.y;
+  const double dn = (double)n;
+  const double mean = stats[0] / dn;
+  const double var = n > 1 ? (stats[1] - stats[0] * stats[0] / dn) / (dn - 1.0) : 0.0;
+  const double thr = mean + stddev_mul * sqrt(var);
+  keep[off + orig] = dist_all[off + orig] <= thr ? 1u : 0u;
+}
+void launch_pfb_statistical(hipStream_t s, const CloudDesc* descs, int ncloud, int max_m, const int* keep_off, const double* dist, double* stats, double stddev_mul,
+                            unsigned* keep) {
+  if (ncloud <= 0 || max_m <= 0) return;
+  hipLaunchKernelGGL(k_pfb_dist_stats, dim3(ncloud), dim3(kBlock), 0, s, descs, keep_off, dist, stats);
+  hipLaunchKernelGGL(k_pfb_statistical_flags, dim3((max_m + kBlock - 1) / kBlock, ncloud), dim3(kBlock), 0, s, descs, keep_off, dist, stats, stddev_mul, keep);
+}
+
 // ------------------------------------------------------------------------------------------------ floor detection
 // FloorDetectionNodelet::detect (apps/floor_detection_nodelet.cpp:110-180; hgs_floor.h).  The clip and the normal filter are flag kernels in front of
 // the prefilter's scan + k_pf_compact; the normals come from k_knn_cov's staged fp64 neighbourhood covariances.  RANSAC is a dense counting problem:

@@ -245,6 +245,12 @@ class RegistrationHIP:
         self._check(L.lib().hgs_prefilter_batch(self._h, sweeps, n, C.byref(params), out))
         return [DeviceCloud._adopt(self, C.c_void_p(out[i])) for i in range(n)]
 
+    def prefilter_batch_stats(self) -> dict:
+        """hgs_debug_prefilter_batch_stats of the engine's last prefilter_batch: sweeps, batched, readbacks, index_builds, tree_launches."""
+        v = [C.c_int32() for _ in range(5)]
+        self._check(L.lib().hgs_debug_prefilter_batch_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("sweeps", "batched", "readbacks", "index_builds", "tree_launches"), (x.value for x in v)))
+
     def map_cloud(self, keyframes, poses, resolution: float) -> DeviceCloud:
         """MapCloudGenerator::generate (src/hdl_graph_slam/map_cloud_generator.cpp:13-51) over resident keyframe clouds."""
         n = len(keyframes)

@@ -309,9 +309,10 @@ int hgs_prefilter_framed(hgs_handle* h, const void* pts, size_t n, size_t stride
  * intensities; a result depends on its own sweep's points only.  One parameter set for all sweeps (one nodelet configuration); the gyro sample, the scan
  * period and the mount matrix are per sweep, each with hgs_prefilter_framed's meaning.  The S LiDARs of one sweep time, or the next sweeps of a recorded run
  * that is replayed into a map, cost one launch sequence and one read-back instead of S: the sweeps lie concatenated on the device, the voxel grids share
- * one sort (sweep ordinal in the key bits above the voxel index) and one scan per compaction.  Batched this way: downsample NONE or VOXELGRID with outlier
- * removal NONE, or RADIUS on the voxel grid (radius_radius / downsample_resolution <= 4: every launch file that selects RADIUS).  Every other parameter
- * set, and a call with one sweep, runs the single-sweep sequence per sweep inside the call, with the same results.
+ * one sort (sweep ordinal in the key bits above the voxel index) and one scan per compaction.  Batched this way: downsample NONE or VOXELGRID with every
+ * outlier removal — none, RADIUS on the voxel grid (radius_radius / downsample_resolution <= 4), and STATISTICAL (the nodelet's default) or RADIUS on a
+ * search tree per sweep: those sweeps' trees come from one index build and their flags from one launch, two read-backs per call whatever S is.  Only
+ * APPROX_VOXELGRID and a call with one sweep run the single-sweep sequence per sweep inside the call, with the same results.
  * n_sweeps == 0: HGS_OK.  A sweep with n == 0 yields an empty cloud.  HGS_ERR_INVALID_ARGUMENT, with nothing touched, for a NULL array, for a sweep that
  * hgs_prefilter_framed would refuse (stride, n > 2^30, a non-finite scan period next to a gyro sample, a matrix with a non-finite entry or another bottom
  * row than 0 0 0 1), for more than 2^30 points in total and for more than HGS_PREFILTER_BATCH_MAX_SWEEPS sweeps (the ordinal bits of the sort key).  A
@@ -448,6 +449,12 @@ int hgs_debug_floor_ransac_counts(hgs_handle* h, hgs_cloud* cloud, const hgs_flo
  * synchronisations that wait for device results): one per compaction stage in front of RANSAC, one for the final counts and states, one between two
  * launch groups ("floor_batch_group") — never one per cloud.  Any pointer may be NULL.  An additive debug symbol. */
 int hgs_debug_floor_batch_stats(hgs_handle* h, int32_t* clouds, int32_t* ransac_clouds, int32_t* ransac_rounds, int32_t* readbacks);
+/* The engine's last hgs_prefilter_batch: *sweeps = the sweeps it took, *batched = 1 when the batch sequence ran, 0 when the sweeps ran one after the
+ * other (one sweep, APPROX_VOXELGRID, "prefilter_batch_tree" = 0 under a parameter set that needs a search tree), *readbacks = the blocking host
+ * read-backs of device results it made, *index_builds = the search-index builds (one per call in the batch sequence, one per sweep otherwise),
+ * *tree_launches = the launches of the batch's tree-walk flag kernels (k_pfb_radius_flags / k_pfb_mean_knn_dist: at most 1).  Any pointer may be NULL.
+ * An additive debug symbol. */
+int hgs_debug_prefilter_batch_stats(hgs_handle* h, int32_t* sweeps, int32_t* batched, int32_t* readbacks, int32_t* index_builds, int32_t* tree_launches);
 /* Valid Gaussian cells of the NDT target (any order): linear key, grid coordinates, mean, inverse covariance, count. */
 int hgs_debug_ndt_cells(hgs_handle* h, int32_t cap, int32_t* ijk3, double* mean3, float* icov6, int32_t* npts, int32_t* n_cells);
 /* Voxels of the FAST_VGICP target's Gaussian voxel map (any order), built for the engine's resolution and correspondence_randomness if needed:
@@ -483,7 +490,7 @@ int hgs_debug_batch_order(hgs_handle* h, int32_t* order, int32_t cap, int32_t* n
 /* A measurement / test knob of one engine: "batch_lanes", "lane_start", "lane_order" (1: a FAST_GICP / FAST_VGICP batch of 8 or more problems that opens
  * several lanes runs the half whose guesses lie farthest from the target on highest-priority streams; records are handed back in the caller's order), "ndt_sort", "cov_split", "resident_descs", "knn_qpw_tiny",
  * "seed_grid", "knn_replay", "ndt_resident", "ndt_chunk", "hilbert_levels", "nn_qpw", "nn_qpw16_below", "nn_qpw32_below", "fused_rounds", "fused_rounds_below", "fused_rounds_max_problems", "fused_rounds_max_blocks", "early_result", "early_run_ahead",
- * "knn_tiny_below", "upload_trace", "prefilter_fast", "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "floor_batch_group" (clouds per RANSAC launch group of
+ * "knn_tiny_below", "upload_trace", "prefilter_fast", "prefilter_batch_tree" (0: hgs_prefilter_batch runs the outlier removals that need a search tree sweep after sweep), "floor_chunk" (hypotheses per RANSAC round of hgs_detect_floor, 1..4096), "floor_batch_group" (clouds per RANSAC launch group of
  * hgs_detect_floor_batch, 0 = all that its work buffers allow), "pair_chunk" (pairs per launch of hgs_calc_fitness_score_batch, 0 = 65535).  Results never depend on them (the tests
  * that force a code path check exactly that); A/B runs and those tests are the only callers — the library reads no tuning variable from the environment. */
 int hgs_debug_set_option(hgs_handle* h, const char* key, int32_t value);
